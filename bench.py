@@ -12,8 +12,14 @@ into pinned host memory.  `value` = targets/s of the whole pipeline INCLUDING re
 (targets/s = n_targets / (walk + graph kernels + D2H)); the kernel-only rate is
 reported beside it.  Targets and table are in HBM before the timed region starts.  The
 `--inflight` workspaces each hold a DIFFERENT 10 000-target set (working set >> the 256 MiB
-Infinity Cache), and the run checks 200 targets against the plain-C oracle given the full key
-set, exiting non-zero on a mismatch.
+Infinity Cache).
+
+A plain run sets up, warms up, times exactly --steps pipelined steps once and prints the headline
+line.  With --full it also repeats the timed region (--repeats, value = the median), checks 200 + 200
+targets against the plain-C oracle given the full key set (non-zero exit on a mismatch) and measures
+everything else the line reports: CPU baselines, kernel-only and full-delivery rates, per-kernel
+times and the roofline, the hard workload, end to end, ingestion, config 5, probe kernels.
+--dump-outputs DIR writes the lean delivery of the last timed step as DIR/<array>.npy (float64).
 
 With --gpus N > 1 and no torchrun environment the script starts N ranks itself
 (python -m torch.distributed.run, before any GPU call) and relays rank 0's JSON line.  The table
@@ -394,6 +400,34 @@ def c_abi_end_to_end(case, args, n_fl):
     return res
 
 
+DUMP_BUDGET = 64 << 20          # bytes of .npy data --dump-outputs may write
+
+
+def dump_outputs(view, path):
+    """The lean delivery of one batch (what km_batch_result hands a caller) as float64 .npy files: every
+    array of the view, node counts as the consumers read them (16-bit values with their escapes applied),
+    the 62-bit walk-discovered k-mers split into two exact 31-bit halves.  Arrays are dumped whole while
+    they fit DUMP_BUDGET; past it each array keeps a fixed seeded sample of its elements, in order, and
+    <name>_index.npy says which."""
+    arrays = {}
+    for name in ("status", "n_ref", "probes", "ref_max_cov", "node_off", "node_count", "extra_off", "path_off",
+                 "run_off", "run_start", "run_len", "path_len", "path_min_cov"):
+        arrays[name] = np.asarray(view[name])
+    xk = np.asarray(view["extra_kmer"], dtype=np.uint64)
+    arrays["extra_kmer_hi"] = xk >> np.uint64(31)
+    arrays["extra_kmer_lo"] = xk & np.uint64((1 << 31) - 1)
+    total = sum(a.size for a in arrays.values()) * 8
+    keep = min(1.0, DUMP_BUDGET / 2 / max(1, total))      # / 2: room for the index arrays
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(20260101)
+    for name, a in arrays.items():
+        if keep < 1.0:
+            idx = np.sort(rng.choice(a.size, size=int(a.size * keep), replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -406,8 +440,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200,
-                    help="steps of the timed region (x --repeats; 200 x 0.15 ms = 30 ms per repeat: round 3's 40 steps were "
-                         "3.5 ms, shorter than the run-to-run effects they were compared against)")
+                    help="steps of the timed region (with --full x --repeats; 200 x 0.15 ms = 30 ms per repeat: round 3's "
+                         "40 steps were 3.5 ms, shorter than the run-to-run effects they were compared against)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: repeats of the timed region, oracle checks, CPU baselines, "
+                         "per-kernel times and roofline, the other workloads and configurations (see the module doc)")
+    ap.add_argument("--dump-outputs", default="",
+                    help="write the lean delivery of the last timed step into this directory as <array>.npy (float64)")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--targets", type=int, default=10000, help="targets per GPU per step")
     ap.add_argument("--length", type=int, default=500)
@@ -443,8 +482,9 @@ def main():
                          "kernel + memory-copy timeline of tools/collect_evidence.sh)")
     ap.add_argument("--no-hard", dest="hard", action="store_false",
                     help="skip the second workload (config4_hard: several variants per target, branch noise, large-tier walks)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="how often the timed region (exactly --steps steps) is repeated; value = the median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how often the timed region (exactly --steps steps) is repeated; value = the median "
+                         "(default: 5 with --full, else 1)")
     ap.add_argument("--one-at-a-time", action="store_true",
                     help="run the batches strictly one after the other (run, wait for the delivery, next batch), still rotating "
                          "over the --inflight distinct target sets: with --serial every launch of a profile is then a kernel "
@@ -456,6 +496,10 @@ def main():
     ap.add_argument("--inflight", type=int, default=4,
                     help="batch workspaces in flight on separate HIP streams (software pipelining)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     # ---- N > 1 without a torchrun environment: start the ranks ourselves, before any GPU call
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -496,7 +540,7 @@ def main():
     if rank == 0:
         import __graft_entry__ as ge
         ge.build()
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             cpu = cpu_baseline(case, min(args.cpu_sample, T))
 
     from km_amd import lib as kmlib
@@ -577,12 +621,12 @@ def main():
     info = db.info
     n_probe = int(min(n_rec, T * (args.length - K + 1)))
     probe_keys = None
-    if rank == 0:
+    if rank == 0 and args.full:
         sel = np.random.default_rng(12345).choice(n_rec, size=n_probe, replace=False)
         probe_keys = np.ascontiguousarray(case["keys"][sel])
 
     # ---- the box's large-copy bandwidth (device-to-device), beside the 8 TB/s spec -------------
-    d2d = kmlib.device_copy_GBs(local_rank, 1 << 30, 10) if rank == 0 else None      # read + write
+    d2d = kmlib.device_copy_GBs(local_rank, 1 << 30, 10) if rank == 0 and args.full else None      # read + write
 
     # ---- workspaces: `inflight` of them, each with its own HIP stream and its OWN target set ---
     # (weak scaling: every rank steps through the same n_fl sets, rotated by its rank)
@@ -669,11 +713,61 @@ def main():
         return vs, float(np.mean([sum(v[x].nbytes for x in v if isinstance(v[x], np.ndarray)
                                       and not (x == "node_count" and "node_count16" in v)) for v in vs]))
 
-    if args.timeline:
-        dts = [timed(deliver, True) for _ in range(max(1, args.repeats))]
-        if rank == 0:
-            print(json.dumps({"timeline_only": True, "ms_per_step": float(np.median(dts)) / args.steps * 1e3,
-                              "steps": args.steps, "repeats": len(dts), "batches_in_flight": n_fl}), flush=True)
+    def headline():
+        """The keys of the line a plain run measures (rank 0)."""
+        ms_per_step = dt / args.steps * 1e3
+        gb = lambda nbytes, ms: nbytes / (ms * 1e-3) / 1e9 if ms > 0 else None
+        return {
+            "metric": "find_mutation_targets_per_sec",
+            "value": world * T / (dt / args.steps),
+            "unit": "targets/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "timed_region": {"repeats": len(dts), "steps_each": args.steps, "value_is": "median",
+                             "ms_per_step_median": ms_per_step, "ms_per_step_min": min(dts) / args.steps * 1e3,
+                             "ms_per_step_max": max(dts) / args.steps * 1e3},
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u64",
+            "data": "synthetic",
+            "config": {"workload": "synthetic_%dx%dnt_targets_per_gpu_%dM_kmer_table_k31"
+                                   % (T, args.length, round(n_rec / 1e6)),
+                       "targets_per_gpu": T, "target_len": args.length, "k": K,
+                       "table_keys": n_rec, "table_bytes": int(info.table_bytes),
+                       "table_bytes_per_kmer": float(info.table_bytes) / max(1, n_rec),
+                       "table_max_probe": int(info.max_probe),
+                       "params": "-c 5 -p 0.05 -s 500 -b 10 -n 10000",
+                       "stages": both_names + " + result delivery (device compaction, D2H to pinned host memory)",
+                       "distinct_target_sets": n_fl,
+                       "value_is": ("BASELINE config 4 on one GPU (10 000 targets x 500 nt, 100 M-key table)" if world == 1 else
+                                    "weak scaling of config 4's shape: %d targets per GPU per step; config 4 PROPER (10 000 targets "
+                                    "sharded over the %d GPUs) is the side key config4_strong" % (T, world)),
+                       "parallelism": "target-sharded x%d, table replicated (records broadcast once over RCCL)" % world},
+            "value_includes": "k_pack, k_seed, k_dfs, k_graph_pure, k_graph, k_out_scan, k_out_pack and the D2H of the "
+                              "lean delivery into pinned host memory",
+            "gprobes_per_s": world * probes_per_step / (dt / args.steps) / 1e9,
+            "delivered_bytes_per_step": out_bytes,
+            "d2h_GBs_inside_pipeline": gb(out_bytes, ms_per_step),
+            "delivery": "lean (KM_DELIVER_LEAN | KM_DELIVER_COUNT16): statuses, probes, paths, min coverages, "
+                        "walk-discovered k-mers and the counts of every target that has them or more than one path "
+                        "(16-bit values + the exact counts >= 65535 in a list); a bare-reference target "
+                        "(one Reference row in the TSV) is delivered as path + min coverage + max count",
+            "logical_probes_per_step": probes_per_step,
+            "table_fetches_per_step": fetches_per_step,
+            "targets_in_large_tier": int(sizes[0].n_big_tier), "targets_flagged": int(sizes[0].n_flagged),
+            "host_loop": ("python (wait_result + run per step)" if args.py_loop else
+                          "km_batch_pump: the round-robin loop over the batches in flight runs inside the library"),
+            "batches_in_flight": n_fl,
+            "hipgraph_replay": bool(args.hipgraph),
+            "ranks_seen": ranks_seen,
+            "setup_s": {"generate": t_gen, "h2d_broadcast": t_bcast, "table_build": t_build},
+        }
+
+    def finish(rc):
+        # release the library's device / pinned memory while the HIP runtime is still up
         for bq in batches:
             bq.close()
         for st_ in tstreams:
@@ -682,19 +776,34 @@ def main():
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
-        sys.exit(0)
-    # full delivery first (every node count crosses PCIe), then the lean one that `value` reports
-    pipeline(n_fl, deliver_full, True)
-    dt_full = timed(deliver_full, True)
-    views_full, out_bytes_full = delivered_bytes()
-    check_full = None
-    if rank == 0 and args.check > 0 and not args.walk_only:
-        check_full = oracle_check(case, views_full, set_ids, T, max(n_fl, args.check // 4))
-    del views_full
-    pipeline(n_fl, deliver, True)
+        sys.exit(rc)
+
+    if args.timeline:
+        dts = [timed(deliver, True) for _ in range(max(1, args.repeats))]
+        if rank == 0:
+            print(json.dumps({"timeline_only": True, "ms_per_step": float(np.median(dts)) / args.steps * 1e3,
+                              "steps": args.steps, "repeats": len(dts), "batches_in_flight": n_fl}), flush=True)
+        finish(0)
+    # --full: full delivery first (every node count crosses PCIe), then the lean one that `value` reports
+    if args.full:
+        pipeline(n_fl, deliver_full, True)
+        dt_full = timed(deliver_full, True)
+        views_full, out_bytes_full = delivered_bytes()
+        check_full = None
+        if rank == 0 and args.check > 0 and not args.walk_only:
+            check_full = oracle_check(case, views_full, set_ids, T, max(n_fl, args.check // 4))
+        del views_full
+        pipeline(n_fl, deliver, True)
     dts = [timed(deliver, True) for _ in range(max(1, args.repeats))]      # each: exactly K steps
     dt = float(np.median(dts))
     views, out_bytes = delivered_bytes()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(views[(args.steps - 1) % n_fl], args.dump_outputs)    # step i ran on batch i % n_fl
+    if not args.full:
+        del views
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        finish(0)
     # the same timed region driven from the interpreter (wait_result + run per step), for the record
     dt_py = None
     if not args.py_loop:
@@ -968,7 +1077,6 @@ def main():
     rc = 0
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
-        value = world * T / (dt / args.steps)
         ms_kernel = dt_kernel / args.steps * 1e3
         gb = lambda nbytes, ms: nbytes / (ms * 1e-3) / 1e9 if ms > 0 else None
         alg_walk = probes_per_step * BYTES_PER_PROBE
@@ -990,53 +1098,14 @@ def main():
                                   "commit": pj.get("commit"), "round": pj.get("round")}
             except Exception:
                 traffic = traffic_source = None
-        out = {
-            "metric": "find_mutation_targets_per_sec",
-            "value": value,
-            "unit": "targets/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "timed_region": {"repeats": len(dts), "steps_each": args.steps, "value_is": "median",
-                             "ms_per_step_median": ms_per_step, "ms_per_step_min": min(dts) / args.steps * 1e3,
-                             "ms_per_step_max": max(dts) / args.steps * 1e3},
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic",
-            "config": {"workload": "synthetic_%dx%dnt_targets_per_gpu_%dM_kmer_table_k31"
-                                   % (T, args.length, round(n_rec / 1e6)),
-                       "targets_per_gpu": T, "target_len": args.length, "k": K,
-                       "table_keys": n_rec, "table_bytes": int(info.table_bytes),
-                       "table_bytes_per_kmer": float(info.table_bytes) / max(1, n_rec),
-                       "table_max_probe": int(info.max_probe),
-                       "params": "-c 5 -p 0.05 -s 500 -b 10 -n 10000",
-                       "stages": both_names + " + result delivery (device compaction, D2H to pinned host memory)",
-                       "distinct_target_sets": n_fl,
-                       "value_is": ("BASELINE config 4 on one GPU (10 000 targets x 500 nt, 100 M-key table)" if world == 1 else
-                                    "weak scaling of config 4's shape: %d targets per GPU per step; config 4 PROPER (10 000 targets "
-                                    "sharded over the %d GPUs) is the side key config4_strong" % (T, world)),
-                       "parallelism": "target-sharded x%d, table replicated (records broadcast once over RCCL)" % world},
-            "value_includes": "k_pack, k_seed, k_dfs, k_graph_pure, k_graph, k_out_scan, k_out_pack and the D2H of the "
-                              "lean delivery into pinned host memory",
-            "gprobes_per_s": world * probes_per_step / (dt / args.steps) / 1e9,
+        out = headline()
+        out.update({
             "kernel_only": {"value": world * T / (dt_kernel / args.steps), "ms_per_step": ms_kernel,
                             "note": "same steps without result delivery (results left in HBM)"},
-            "delivered_bytes_per_step": out_bytes,
-            "d2h_GBs_inside_pipeline": gb(out_bytes, ms_per_step),
-            "delivery": "lean (KM_DELIVER_LEAN | KM_DELIVER_COUNT16): statuses, probes, paths, min coverages, "
-                        "walk-discovered k-mers and the counts of every target that has them or more than one path "
-                        "(16-bit values + the exact counts >= 65535 in a list); a bare-reference target "
-                        "(one Reference row in the TSV) is delivered as path + min coverage + max count",
             "full_delivery": {"value": world * T / (dt_full / args.steps), "ms_per_step": dt_full / args.steps * 1e3,
                               "delivered_bytes_per_step": out_bytes_full,
                               "deliver_kernels_ms": outk_full, "d2h_copy_ms": d2h_full, "oracle_check": check_full,
                               "note": "same pipeline with the counts of EVERY node crossing PCIe"},
-            "logical_probes_per_step": probes_per_step,
-            "table_fetches_per_step": fetches_per_step,
-            "targets_in_large_tier": int(sizes[0].n_big_tier), "targets_flagged": int(sizes[0].n_flagged),
             "kernel_ms": {"walk": walk_avg, "walk_stage_events_only": walk_stage_avg, "k_pack": pack_avg, "k_seed": seed_avg, "k_dfs": dfs_avg,
                           "graph": graph_avg, "deliver_kernels": outk_avg, "d2h_copy": d2h_avg,
                           "note": "one batch at a time, every kernel alone on the GPU (KM_RUN_SERIAL), HIP events "
@@ -1044,16 +1113,11 @@ def main():
                           "as_pipelined": {"walk": ovl[0], "k_seed": ovl[3], "k_dfs": ovl[5], "graph": ovl[1],
                                            "note": "the same with k_graph_pure beside k_dfs on the side stream, "
                                                    "as every other number of this line runs it"}},
-            "host_loop": ("python (wait_result + run per step)" if args.py_loop else
-                          "km_batch_pump: the round-robin loop over the batches in flight runs inside the library"),
             "ms_per_step_python_loop": (dt_py / args.steps * 1e3) if dt_py else None,
-            "batches_in_flight": n_fl,
-            "hipgraph_replay": bool(args.hipgraph),
             "ms_per_step_unpipelined": serial_ms,
             "result_fetch_ms": outk_avg + d2h_avg,
             "result_fetch_copying_api_ms": fetch_s * 1e3,
             "oracle_check": check,
-            "ranks_seen": ranks_seen,
             "config4_strong": strong,
             "config4_strong_ceiling_measured_on_one_gpu": strong_ceiling,
             "config4_hard": hard,
@@ -1063,7 +1127,6 @@ def main():
             "single_target_latency": single,
             "probe_kernels": probe,
             "d2d_copy_GBs": d2d,
-            "setup_s": {"generate": t_gen, "h2d_broadcast": t_bcast, "table_build": t_build},
             "jf_ingestion": ingest,
             # achieved = logical probes x 12 B / walk-stage time
             "roofline": {"bound": "hbm", "kernel": "walk stage (k_pack + k_seed + k_dfs)",
@@ -1085,7 +1148,7 @@ def main():
                              "whole_step_pipelined": {"achieved": gb(alg_walk, ms_per_step),
                                                       "frac": gb(alg_walk, ms_per_step) / HBM_PEAK_GBS}}},
             "cpu_baseline": cpu,
-        }
+        })
         print(json.dumps(out), flush=True)
         if check is not None and not check["ok"]:
             log("ORACLE CHECK FAILED:", check)
@@ -1093,17 +1156,7 @@ def main():
         if hard is not None and not hard["oracle_check"]["ok"]:
             log("ORACLE CHECK FAILED (config4_hard):", hard["oracle_check"])
             rc = 3
-    # release the library's device / pinned memory while the HIP runtime is still up
-    for bq in batches:
-        bq.close()
-    del batches, batch
-    for st_ in tstreams:
-        kmlib.stream_destroy(st_)
-    db.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    sys.exit(rc)
+    finish(rc)
 
 
 if __name__ == "__main__":

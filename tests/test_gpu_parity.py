@@ -1269,7 +1269,7 @@ def test_bench_line_at_two_ranks():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(29600 + os.getpid() % 300), os.path.join(root, "bench.py"), "--gpus", "2",
            "--steps", "6", "--warmup", "2", "--keys", "3000000", "--targets", "2000", "--no-cpu", "--e2e", "0",
-           "--no-ingest", "--no-hard", "--repeats", "2"] + ([] if two else ["--one-gpu", "--backend", "gloo"])
+           "--no-ingest", "--no-hard", "--repeats", "2", "--full"] + ([] if two else ["--one-gpu", "--backend", "gloo"])
     p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -1282,6 +1282,35 @@ def test_bench_line_at_two_ranks():
     assert d["ranks_seen"]["world_size"] == 2 and len(d["ranks_seen"]["devices"]) == 2
     assert d["oracle_check"]["ok"] and d["config4_strong"]["scaling"] == "strong"
     assert d["timed_region"]["repeats"] == 2
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run: the headline keys only (what --full adds is absent), exactly --steps timed steps, and
+    --dump-outputs writes the lean delivery of the last step as float64 arrays whose offsets agree with their
+    lengths."""
+    import subprocess
+    import sys
+    root = os.path.dirname(HERE)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--keys", "3000000",
+           "--targets", "2000", "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    for key in ("roofline", "oracle_check", "kernel_ms", "cpu_baseline", "config4_hard", "end_to_end_c_abi"):
+        assert key not in d, key
+    assert d["steps"] == 5 and d["timed_region"]["repeats"] == 1 and d["value"] > 0
+    out = {f[:-4]: np.load(str(tmp_path / "out" / f)) for f in os.listdir(str(tmp_path / "out"))}
+    assert all(a.dtype == np.float64 for a in out.values())
+    n = out["status"].size
+    assert n == 2000 and out["node_off"].size == out["path_off"].size == n + 1
+    assert out["node_off"][-1] == out["node_count"].size and out["extra_off"][-1] == out["extra_kmer_hi"].size
+    assert out["path_off"][-1] == out["path_min_cov"].size == out["path_len"].size
+    assert out["run_off"][-1] == out["run_start"].size == out["run_len"].size
+    assert (out["probes"] > 0).all()
 
 
 def test_config5_synthetic_samples_match_oracle(tmp_path):

@@ -2,7 +2,7 @@
 # Round evidence on the GPU box: kernel trace + stats (every kernel alone, ROTATING over four distinct target sets:
 # no launch replays the set of the launch before it out of the 256 MiB Infinity Cache), PMC passes (separate runs, as
 # the guide prescribes), the same three for the second workload (config4_hard), a kernel + memory-copy timeline of the
-# PIPELINED step (what `value` measures), the default bench line.  Results under gpurun_out/$1/ ; copy what is to be
+# PIPELINED step (what `value` measures), the `bench.py --full` line.  Results under $out (below) ; copy what is to be
 # judged into profiles/.
 set -o pipefail
 tag=${1:-r04}
@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 python3 -c "import __graft_entry__ as g; g.build()" || exit 1
 # --serial: each kernel alone on the GPU (KM_RUN_SERIAL); --inflight 4 --one-at-a-time: four batches with their own
 # target sets, run strictly one after the other — what bench.py's own HIP events (roofline.frac) time
-B="python3 bench.py --steps 20 --warmup 4 --no-cpu --only-step --check 0 --inflight 4 --one-at-a-time --serial --repeats 1 --cache /tmp/kmc"
+B="python3 bench.py --full --steps 20 --warmup 4 --no-cpu --only-step --check 0 --inflight 4 --one-at-a-time --serial --repeats 1 --cache /tmp/kmc"
 H="python3 bench.py --steps 16 --warmup 4 --no-cpu --profile-hard --inflight 2 --cache /tmp/kmc"
 python3 bench.py --dump-case /tmp/kmc_client --cache /tmp/kmc || exit 1
 P="km_amd/kmclient pump /tmp/kmc_client 40 8 4 3"
@@ -43,5 +43,5 @@ rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_INS
 mkdir -p $out/pmc3
 python3 tools/pmc_summary.py $out $out/hard_pmc_summary.json ${tag}_hard
 rm -rf $out/pmc1 $out/pmc2 $out/pmc3 $out/pmc4
-echo "[9/9] default bench"; python3 bench.py --cache /tmp/kmc > $out/bench_N1.json 2> $out/bench_N1.err || exit 1
+echo "[9/9] full bench line"; python3 bench.py --full --cache /tmp/kmc > $out/bench_N1.json 2> $out/bench_N1.err || exit 1
 tail -c 400 $out/bench_N1.json

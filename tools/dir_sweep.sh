@@ -3,7 +3,7 @@
 out=gpurun_out/${1:-dirsweep}; mkdir -p $out
 python3 -c "import __graft_entry__ as g; g.build()" || exit 1
 for lg in ${DIR_LOGS:-27 26 25 24}; do
-  KM_DIR_LOG2=$lg timeout -k 10 500 python3 bench.py --no-cpu --only-step --steps 40 --repeats 3 --no-hard --cache /tmp/kmc > $out/bench_$lg.json 2> $out/bench_$lg.err || { tail -3 $out/bench_$lg.err; continue; }
+  KM_DIR_LOG2=$lg timeout -k 10 500 python3 bench.py --full --no-cpu --only-step --steps 40 --repeats 3 --no-hard --cache /tmp/kmc > $out/bench_$lg.json 2> $out/bench_$lg.err || { tail -3 $out/bench_$lg.err; continue; }
   python3 - $out/bench_$lg.json $lg <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ mkdir -p $out
 python3 -c "import __graft_entry__ as g; g.build()" || exit 1
 for so in km_amd/variants/*.so; do
   n=$(basename $so .so)
-  KM_LIBRARY=$PWD/$so timeout -k 10 500 python3 bench.py --no-cpu --only-step --steps 20 --repeats 3 --cache /tmp/kmc > $out/bench_$n.json 2> $out/bench_$n.err || { tail -5 $out/bench_$n.err; exit 1; }
+  KM_LIBRARY=$PWD/$so timeout -k 10 500 python3 bench.py --full --no-cpu --only-step --steps 20 --repeats 3 --cache /tmp/kmc > $out/bench_$n.json 2> $out/bench_$n.err || { tail -5 $out/bench_$n.err; exit 1; }
   python3 - $out/bench_$n.json $n <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -202,10 +202,17 @@ int kmjf_children_batch_dev(kmjf_t* h, const uint64_t* d_kmers, uint64_t n, doub
 int km_batch_create(kmjf_t* h, const km_params_t* params, uint32_t max_targets,
                     uint64_t max_total_bases, km_batch_t** out);
 int km_batch_destroy(km_batch_t* b);
-/* Targets as concatenated ASCII bases (ACGT, either case); offsets[n+1]. Copies H2D. */
+/* Targets as concatenated ASCII bases (ACGT, either case); offsets[n+1]. Copies H2D.
+ * Failure: every argument is checked first (n_targets <= max_targets, offsets non-decreasing, no target
+ * longer than 2^31 - 1 bases, offsets[n] - offsets[0] <= max_total_bases); a rejected call (KM_E_ARG)
+ * changes nothing: the batch keeps its targets, and the next run gives the results it gave before.
+ * In flight: the call may follow a km_batch_run whose results were never awaited (any stream): it first
+ * waits for that run and its delivery, then discards them.  Either way, views handed out by an earlier
+ * km_batch_result of this batch are invalid once the call has succeeded. */
 int km_batch_set_targets(km_batch_t* b, const uint8_t* bases, const uint64_t* offsets,
                          uint32_t n_targets);
-/* Same with device-resident arrays (copied device-to-device, async on stream). */
+/* Same with device-resident arrays (copied device-to-device, async on stream; the call returns once the
+ * copy is done).  Same failure guarantee and in-flight behaviour. */
 int km_batch_set_targets_dev(km_batch_t* b, const uint8_t* d_bases, const uint64_t* offsets_host,
                              uint32_t n_targets, void* stream);
 #define KM_STAGE_WALK  1

@@ -1166,11 +1166,30 @@ extern "C" int km_batch_destroy(km_batch_t* b) {
 
 static uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
 
-// Per-batch geometry + per-target node storage layout.
-static int layout_targets(km_batch* b, const uint64_t* offsets, uint32_t n) {
+// Every check of a new target set, before anything of the batch is touched: a rejected set leaves the
+// batch as it was (same targets, same results on the next run).
+static int check_targets(const km_batch* b, const uint64_t* offsets, uint32_t n) {
   if (n > b->max_targets) return fail(KM_E_ARG, "too many targets for this batch (%u > %u)", n, b->max_targets);
+  for (uint32_t t = 0; t < n; ++t) {
+    if (offsets[t + 1] < offsets[t]) return fail(KM_E_ARG, "offsets must be non-decreasing");
+    if (offsets[t + 1] - offsets[t] > 0x7FFFFFFFull) return fail(KM_E_ARG, "target too long");
+  }
+  if (offsets[n] - offsets[0] > b->max_bases) return fail(KM_E_ARG, "too many bases for this batch");
+  return KM_OK;
+}
+
+// A step of the old set may still be running (an un-awaited km_batch_run): its kernels and its delivery copy
+// read the inputs and the layout that the new set overwrites.  The batch's streams are non-blocking, so
+// neither hipMemcpy nor a synchronisation of the NULL stream orders against them: wait for the last one.
+// After an awaited delivery (result_ready) nothing of this batch is left in that stream.
+static int wait_in_flight(km_batch* b) {
+  if (b->deliver_pending || (!b->synced && !b->result_ready)) HIPCHK(hipStreamSynchronize(b->last_stream));
+  return KM_OK;
+}
+
+// Per-batch geometry + per-target node storage layout (offsets passed check_targets).
+static int layout_targets(km_batch* b, const uint64_t* offsets, uint32_t n) {
   const uint64_t total = offsets[n] - offsets[0];
-  if (total > b->max_bases) return fail(KM_E_ARG, "too many bases for this batch");
   const int k = b->db->k;
   b->h_toff.assign(n + 1, 0);
   b->h_woff.assign(n + 1, 0);
@@ -1182,9 +1201,7 @@ static int layout_targets(km_batch* b, const uint64_t* offsets, uint32_t n) {
   b->big_region = 0;
   uint32_t max_len = 0;
   for (uint32_t t = 0; t < n; ++t) {
-    if (offsets[t + 1] < offsets[t]) return fail(KM_E_ARG, "offsets must be non-decreasing");
     const uint64_t L = offsets[t + 1] - offsets[t];
-    if (L > 0x7FFFFFFFull) return fail(KM_E_ARG, "target too long");
     b->h_toff[t] = offsets[t] - offsets[0];
     b->h_woff[t + 1] = b->h_woff[t] + (L + 31) / 32 + 1;
     const uint32_t n_ref = (L >= (uint64_t)k) ? (uint32_t)(L - k + 1) : 0;
@@ -1244,8 +1261,12 @@ static int push_layout(km_batch* b, hipStream_t st) {
 extern "C" int km_batch_set_targets(km_batch_t* b, const uint8_t* bases, const uint64_t* offsets,
                                     uint32_t n_targets) {
   if (!b || !offsets || (!bases && n_targets)) return fail(KM_E_ARG, "null argument");
+  int rc = check_targets(b, offsets, n_targets);
+  if (rc != KM_OK) return rc;
   HIPCHK(hipSetDevice(b->device));
-  int rc = layout_targets(b, offsets, n_targets);
+  rc = wait_in_flight(b);
+  if (rc != KM_OK) return rc;
+  rc = layout_targets(b, offsets, n_targets);
   if (rc != KM_OK) return rc;
   if (b->total_bases)
     HIPCHK(hipMemcpy(b->d_bases.p, bases + offsets[0], b->total_bases, hipMemcpyHostToDevice));
@@ -1255,8 +1276,12 @@ extern "C" int km_batch_set_targets(km_batch_t* b, const uint8_t* bases, const u
 extern "C" int km_batch_set_targets_dev(km_batch_t* b, const uint8_t* d_bases,
                                         const uint64_t* offsets_host, uint32_t n_targets, void* stream) {
   if (!b || !offsets_host || (!d_bases && n_targets)) return fail(KM_E_ARG, "null argument");
+  int rc = check_targets(b, offsets_host, n_targets);
+  if (rc != KM_OK) return rc;
   HIPCHK(hipSetDevice(b->device));
-  int rc = layout_targets(b, offsets_host, n_targets);
+  rc = wait_in_flight(b);
+  if (rc != KM_OK) return rc;
+  rc = layout_targets(b, offsets_host, n_targets);
   if (rc != KM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (b->total_bases)

@@ -337,6 +337,20 @@ int km_batch_debug_stamps(km_batch_t* b, uint64_t* dst, uint64_t cap_words, uint
  * the pure-chain pass handed to k_graph, [2] flagged targets the epilogue of k_dfs left to k_graph, [3] 0. */
 int km_batch_debug_counts(km_batch_t* b, uint32_t* out4);
 
+/* ---- linear_kmin -------------------------------------------------------------------------------
+ * `km linear_kmin` (km/tools/linear_kmin.py:7-46) for a catalog: per target, the smallest k >= start at
+ * which the target's k-mers are unique (km/utils/common.py:48-63: the ValueError / KM_T_REPEAT_KMER of
+ * find_mutation) and their (k-1)-overlap graph is linear; as in the reference's loop, k is at most the
+ * target's length unless start - 1 is larger (then k = start - 1).  Target t is bases[base_off[t] .. base_off[t+1]), ASCII, already upper-cased (any byte
+ * is compared as is, N included).  Optional per-target outputs: longest_repeat = R, the longest repeated
+ * substring (overlaps allowed), and nonexempt = some repeat of length R is not one of the pairs the
+ * linearity test lets pass.  Blocks until the results are in host memory; device buffers
+ * are sized to the call and freed before it returns; large inputs are staged in chunks.  KM_E_ARG, before
+ * any HIP call, for NULL pointers, decreasing offsets or a target longer than 2^31 - 1; n_targets == 0
+ * returns KM_OK without a launch.  stream: a hipStream_t, NULL = one of the library's own. */
+int km_linear_kmin(int device, const uint8_t* bases, const uint64_t* base_off, uint32_t n_targets,
+                   int32_t start, int32_t* kmin, int32_t* longest_repeat, uint8_t* nonexempt, void* stream);
+
 /* ---- measurement helpers (bench.py at N = 1 holds no device buffers of its own) ------------- */
 int km_device_sync(int device);                                    /* hipDeviceSynchronize on `device`          */
 /* device-to-device copy of `bytes` bytes, `reps` times: read + write GB/s (the box's large-copy

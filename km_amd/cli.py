@@ -1,4 +1,4 @@
-"""``km find_mutation`` / ``km min_cov`` drop-in command line.
+"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line.
 
 Same flags, same ``#key:value`` echo, same TSV and ``#Elapsed time`` trailer as
 km/tools/find_mutation.py:17-60 and km/argparser/find_mutation.py:4-58, so the
@@ -16,7 +16,7 @@ import time
 
 from . import report
 from .finder import BatchFinder, NodeLimitExceeded
-from .jellyfish import Jellyfish
+from .jellyfish import Jellyfish, default_device
 
 
 def add_find_mutation_args(p):
@@ -55,6 +55,71 @@ def read_target(path):
             elif seen_header:
                 chunks.append(line.strip())
     return "".join(chunks).upper()
+
+
+def read_target_records(path):
+    """The target as ``km linear_kmin`` reads it: km/utils/common.py:25-45 (file_2_seq) joined
+    (km/tools/linear_kmin.py:55-56).  Records are joined and upper-cased, lines before the first header are
+    ignored, consecutive headers count as one (the first is parsed).  The reference's errors are raised
+    with its exception type and text: a header field (``>`` read as ``location=``, fields split at ``|``)
+    without exactly one ``=`` fails its ``k, v = x.split("=")``; a header with no line after it ends its
+    FASTA generator with ``RuntimeError: generator raised StopIteration``."""
+    seqs = []
+    header, lines = None, None
+
+    def finish():
+        for field in header.replace(">", "location=", 1).split("|"):
+            k, v = field.split("=")                  # noqa: F841 - the unpack is the reference's check
+        seqs.append("".join(lines).upper())
+
+    with open(path) as fh:
+        for line in fh:
+            if line.startswith(">"):
+                if lines is not None:
+                    finish()
+                    header, lines = None, None
+                if header is None:
+                    header = line.strip()
+            elif header is not None:
+                if lines is None:
+                    lines = []
+                lines.append(line.strip())
+    if lines is not None:
+        finish()
+    elif header is not None:
+        raise RuntimeError("generator raised StopIteration")
+    return "".join(seqs)
+
+
+def main_linear_kmin(args, out=None):
+    """km/tools/linear_kmin.py:49-61: every target file read first, then ONE km_linear_kmin call for all of
+    them.  Where a file fails to read, the rows of the files before it are printed, then the reference's
+    exception is raised, as the reference (which prints while it goes) leaves it."""
+    out = sys.stdout if out is None else out
+    out.write("target_name\tlinear_kmin\n")
+    if not args.target_fn:
+        raise IndexError("list index out of range")    # km/utils/common.py:13 reads args[0]
+    names, seqs, error = [], [], None
+    for f in list_target_files(args.target_fn):
+        try:
+            seq = read_target_records(f)
+        except Exception as e:                          # noqa: BLE001 - re-raised after the earlier rows
+            error = e
+            break
+        if not seq.isascii():
+            error = SystemExit("ERROR: %s: linear_kmin takes ASCII sequences only (km_amd compares bytes)" % f)
+            break
+        names.append(os.path.splitext(os.path.basename(f))[0])
+        seqs.append(seq)
+    if seqs:
+        if args.start is None:                          # `-s` without a value: what `k_len = start - 1` raises
+            raise TypeError("unsupported operand type(s) for -: 'NoneType' and 'int'")
+        from . import lib
+        kmin = lib.linear_kmin(seqs, start=args.start, device=default_device())
+        out.write("".join("%s\t%d\n" % (name, k) for name, k in zip(names, kmin.tolist())))
+    out.flush()
+    if error is not None:
+        raise error
 
 
 CHUNK = 8192          # targets per GPU batch; rows are flushed after every batch
@@ -240,6 +305,10 @@ def main(argv=None):
     sm.add_argument("-t", "--targets", nargs="+", required=True, help="target FASTA files or one directory")
     sm.add_argument("-o", "--out-dir", required=True)
     sm.add_argument("jellyfish_fn", nargs="+", help="one .jf per sample")
+    lk = sub.add_parser("linear_kmin")
+    lk.add_argument("-s", "--start", help="starting length (default: -s 10)", action="store", nargs="?",
+                    default=10, type=int)
+    lk.add_argument("target_fn", help="Filename of the reference sequence file or directory.", nargs="*")
     args = parser.parse_args(argv)
     cmd = args._cmd
     del args._cmd
@@ -255,6 +324,8 @@ def main(argv=None):
         main_samples(args)
     elif cmd == "min_cov":
         main_min_cov(args)
+    elif cmd == "linear_kmin":
+        main_linear_kmin(args)
     else:
         parser.print_help(sys.stderr)
         sys.exit(1)

@@ -33,7 +33,7 @@ SYMBOLS = [
     "km_batch_set_targets", "km_batch_set_targets_dev", "km_batch_run", "km_batch_sync",
     "km_batch_sizes", "km_batch_fetch", "km_batch_result", "km_batch_timings", "km_batch_graph_log", "km_batch_pump", "km_batch_debug_stamps", "km_batch_debug_counts",
     "km_device_sync", "km_device_copy_GBs", "km_probe_bench",
-    "km_report_rows", "km_report_free", "km_strerror", "km_last_error",
+    "km_report_rows", "km_report_free", "km_linear_kmin", "km_strerror", "km_last_error",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
 ]
 
@@ -197,6 +197,7 @@ def load():
         "km_batch_debug_counts": [vp, C.POINTER(C.c_uint32)],
         "km_report_rows": [C.POINTER(ReportIn), C.POINTER(vp), C.POINTER(C.POINTER(C.c_uint64)),
                            C.POINTER(C.POINTER(C.c_int32))],
+        "km_linear_kmin": [i32, vp, vp, u32, i32, vp, vp, vp, vp],
         "km_device_count": [C.POINTER(i32)],
         "km_device_sync": [i32],
         "km_device_copy_GBs": [i32, u64, i32, C.POINTER(dbl)],
@@ -626,6 +627,20 @@ def pack_sequences(seqs):
     offs = np.zeros(len(enc) + 1, dtype=np.uint64)
     np.cumsum([len(e) for e in enc], out=offs[1:])
     return np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8), offs
+
+
+def linear_kmin(seqs, start=10, device=0, stream=None, detail=False):
+    """`km linear_kmin` (km/tools/linear_kmin.py:7-46) of every sequence (ASCII str or bytes, upper-cased)
+    in one km_linear_kmin call: an int32 array of k.  detail=True also returns R (the longest repeated
+    substring, int32) and the flag (uint8: some repeat of length R is not exempt), DESIGN.md §9."""
+    lib = load()
+    blob, offs = pack_sequences(seqs)
+    n = len(offs) - 1
+    kmin = np.zeros(n, np.int32)
+    rep = np.zeros(n, np.int32)
+    flag = np.zeros(n, np.uint8)
+    check(lib.km_linear_kmin(device, ptr(blob), ptr(offs), n, start, ptr(kmin), ptr(rep), ptr(flag), stream))
+    return (kmin, rep, flag) if detail else kmin
 
 
 def report_rows(res, names, seqs, k, db_name, packed=None):

@@ -12,7 +12,9 @@
 #include <new>
 #include <string>
 #include <map>
+#include <memory>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "../../include/kmgpu.h"
@@ -69,6 +71,61 @@ extern "C" int km_device_count(int* n) {
   return KM_OK;
 }
 
+static int fail_hip(int code, const char* what, hipError_t e) { return fail(code, "%s: %s", what, hipGetErrorString(e)); }
+
+// ------------------------------------------------------------------ owned resources
+// Every buffer, event, graph and file the library makes belongs to one of these, which releases it when the owner goes
+// and reads as the raw handle it holds.  A release happens under the device current at that moment: an owner of another
+// device's resource sets that device first (kmjf::free_table, kmjf_broadcast's Peer).  None lives in static storage
+// (the pool's streams below are plain handles that last as long as the process).
+namespace {
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  uint64_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(DevBuf&& o) noexcept {   // frees what this held, takes what o held
+    release();
+    std::swap(p, o.p);
+    std::swap(n, o.n);
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  operator T*() const { return p; }
+  int alloc(uint64_t count) {
+    if (count <= n && p) return KM_OK;
+    release();
+    if (count == 0) count = 1;
+    hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+    if (e != hipSuccess) { p = nullptr; n = 0; return fail(KM_E_NOMEM, "hipMalloc of %llu bytes failed",
+                                                          (unsigned long long)(count * sizeof(T))); }
+    n = count;
+    return KM_OK;
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+};
+
+template <typename H, auto Free>
+struct Owned {
+  H h;
+  explicit Owned(H v = nullptr) : h(v) {}
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() { reset(); }
+  operator H() const { return h; }
+  void reset() { if (h) (void)Free(h); h = nullptr; }
+};
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Graph = Owned<hipGraph_t, hipGraphDestroy>;
+using GraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
+using Pinned = Owned<unsigned char*, hipHostFree>;
+using File = Owned<FILE*, fclose>;
+struct Unmap { size_t len; void operator()(void* p) const { munmap(p, len); } };
+using Mapping = std::unique_ptr<void, Unmap>;
+}  // namespace
+
 // ---- streams.  A pipelined consumer runs a few batches at a time, each on its own launch stream.  How
 // those streams fall onto the GPU's hardware queues decides how well the batches overlap.  Measured on
 // MI355X, four batches in flight (tools/pump_min.py): with the runtime's default of 4 hardware queues and
@@ -97,7 +154,9 @@ int pool_get(int device, hipStream_t* out) {
   std::lock_guard<std::mutex> lk(g_pool_mu);
   StreamPool& p = g_pools[device];
   if (p.launch.empty()) {
-    for (int i = 0; i < POOL_STREAMS; ++i) { hipStream_t st = nullptr; HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); p.launch.push_back(st); }
+    Stream made[POOL_STREAMS];                     // the pool takes them once all exist
+    for (Stream& s : made) HIPCHK(hipStreamCreateWithFlags(&s.h, hipStreamNonBlocking));
+    for (Stream& s : made) { p.launch.push_back(s.h); s.h = nullptr; }
     p.in_use.assign(p.launch.size(), 0);
   }
   for (size_t i = 0; i < p.launch.size(); ++i)
@@ -142,41 +201,65 @@ struct kmjf {
   uint64_t n_records = 0;
   // device table
   int device = -1;
-  Slot* d_slots = nullptr;
+  DevBuf<Slot> d_slots;
   uint64_t n_slots = 0;
-  uint32_t* d_dir = nullptr;     // [n_buckets + 1] (+ padding) exclusive prefix of bucket sizes
+  DevBuf<uint32_t> d_dir;        // [n_buckets + 1] (+ padding) exclusive prefix of bucket sizes
   uint32_t n_buckets = 0;
   uint32_t unit = 2;
   uint32_t max_probe = 2;
-  OvfSlot* d_ovf = nullptr;
+  DevBuf<OvfSlot> d_ovf;
   uint64_t n_ovf = 0;
   uint64_t n_groups = 0;
+
+  ~kmjf() { free_table(); }
+  void free_table() {
+    if (d_slots) {
+      (void)hipSetDevice(device);
+      d_slots.release();
+      d_ovf.release();
+      d_dir.release();
+    }
+    n_slots = n_groups = n_ovf = 0;
+    n_buckets = 0;
+    device = -1;
+  }
 };
 
 static uint64_t mask_bits(int nbases) { return nbases >= 32 ? ~0ull : ((1ull << (2 * nbases)) - 1); }
 
-static TableView view_of(const kmjf* h) {
+// A table's geometry over its directory: what the build kernels see before there are slots
+static TableView table_shape(int k, int canonical, uint32_t n_buckets, uint32_t unit, const uint32_t* dir) {
   TableView t;
-  t.slots = h->d_slots;
-  t.dir = h->d_dir;
-  t.n_slots = h->n_slots;
-  t.ovf = h->d_ovf;
-  t.n_ovf = h->n_ovf;
-  t.kmask = mask_bits(h->k);
-  t.pmask = mask_bits(h->k - 1);
-  t.n_buckets = h->n_buckets;
+  t.slots = nullptr;
+  t.dir = dir;
+  t.n_slots = 0;
+  t.ovf = nullptr;
+  t.n_ovf = 0;
+  t.kmask = mask_bits(k);
+  t.pmask = mask_bits(k - 1);
+  t.n_buckets = n_buckets;
   t.bshift = 31;                                    // (n_buckets: a power of two, 2^4 .. 2^30; 0 before the build)
-  while (t.bshift > 1 && (1ull << (32 - t.bshift)) < h->n_buckets) --t.bshift;
-  t.unit = h->unit;
-  t.max_probe = h->max_probe;
-  t.k = h->k;
-  t.canonical = h->canonical;
-  t.m = minimizer_len(h->k);
-  t.w = h->k - t.m;
+  while (t.bshift > 1 && (1ull << (32 - t.bshift)) < n_buckets) --t.bshift;
+  t.unit = unit;
+  t.max_probe = 2;
+  t.k = k;
+  t.canonical = canonical;
+  t.m = minimizer_len(k);
+  t.w = k - t.m;
   t.mmask = (uint32_t)mask_bits(t.m);
   t.inv32 = (uint32_t)((1ull << 32) / ((uint64_t)2 * t.w * 256));
   t.cshift = 1;
   while ((1u << t.cshift) < 2u * (uint32_t)t.w) ++t.cshift;
+  return t;
+}
+
+static TableView view_of(const kmjf* h) {
+  TableView t = table_shape(h->k, h->canonical, h->n_buckets, h->unit, h->d_dir);
+  t.slots = h->d_slots;
+  t.n_slots = h->n_slots;
+  t.ovf = h->d_ovf;
+  t.n_ovf = h->n_ovf;
+  t.max_probe = h->max_probe;
   return t;
 }
 
@@ -224,25 +307,7 @@ extern "C" int kmjf_create(int k, int canonical, kmjf_t** out) {
   return kmjf_from_records(nullptr, nullptr, 0, k, canonical, out);
 }
 
-static void free_table(kmjf* h) {
-  if (h->d_slots) {
-    (void)hipSetDevice(h->device);
-    (void)hipFree(h->d_slots);
-    h->d_slots = nullptr;
-    if (h->d_ovf) (void)hipFree(h->d_ovf);
-    h->d_ovf = nullptr;
-    h->n_ovf = 0;
-    if (h->d_dir) (void)hipFree(h->d_dir);
-    h->d_dir = nullptr;
-  }
-  h->n_slots = h->n_groups = 0;
-  h->n_buckets = 0;
-  h->device = -1;
-}
-
 extern "C" int kmjf_close(kmjf_t* h) {
-  if (!h) return KM_OK;
-  free_table(h);
   delete h;
   return KM_OK;
 }
@@ -286,7 +351,7 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
                                        const uint32_t* d_counts, uint64_t n, void* stream) {
   if (!h || (n && (!d_keys || !d_counts))) return fail(KM_E_ARG, "null argument");
   hipStream_t st = (hipStream_t)stream;
-  free_table(h);
+  h->free_table();
   HIPCHK(hipSetDevice(device));
   // every record enters at most two groups
   const uint64_t max_entries = (h->canonical ? 2 : 1) * n;
@@ -306,47 +371,28 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
   if (const char* dl = getenv("KM_DIR_LOG2")) { int v = atoi(dl); if (v >= 4 && v <= 30) n_buckets = 1u << v; }
   const uint32_t n_chunks = (uint32_t)(((uint64_t)n_buckets + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK);
   const uint64_t dir_words = (uint64_t)n_chunks * SCAN_CHUNK;
-  uint32_t* dir = nullptr;
-  uint32_t* caps = nullptr;
-  uint32_t* sums = nullptr;
-  unsigned long long* d_meta = nullptr;   // [0] occupied slots, [1] error, [2] flagged buckets, [3] max probe distance,
-                                          // [4] big counts, [5] total capacity (pairs)
-  Slot* slots = nullptr;
-  uint64_t slots_cap = 0;
-  OvfSlot* ovf = nullptr;
-  uint32_t** ctr_ptr = nullptr;
-  uint32_t* settle_bits = nullptr;      // one bit per bucket: on the list below
-  uint32_t* settle_list = nullptr;      // buckets holding a key outside its home pair (k_table_settle)
+  // the table (dir, slots, ovf) goes to h once built; the rest is build scratch
+  DevBuf<uint32_t> dir, caps, sums;
+  DevBuf<unsigned long long> d_meta;   // [0] occupied slots, [1] error, [2] flagged buckets, [3] max probe distance,
+                                       // [4] big counts, [5] total capacity (pairs)
+  DevBuf<Slot> slots;
+  DevBuf<OvfSlot> ovf;
+  DevBuf<uint32_t> settle_bits;         // one bit per bucket: on the list below
+  DevBuf<uint32_t> settle_list;         // buckets holding a key outside its home pair (k_table_settle)
   const uint32_t SETTLE_CAP = 1u << 22;
   const uint64_t settle_words = ((uint64_t)n_buckets + 31) / 32 + 1;
-  auto bail = [&](int code, const char* what, hipError_t e) {
-    if (dir) (void)hipFree(dir);
-    if (caps) (void)hipFree(caps);
-    if (settle_bits) (void)hipFree(settle_bits);
-    if (settle_list) (void)hipFree(settle_list);
-    if (sums) (void)hipFree(sums);
-    if (d_meta) (void)hipFree(d_meta);
-    if (slots) (void)hipFree(slots);
-    if (ovf) (void)hipFree(ovf);
-    if (ctr_ptr && *ctr_ptr) (void)hipFree(*ctr_ptr);
-    return fail(code, "%s: %s", what, hipGetErrorString(e));
-  };
-  hipError_t e = hipMalloc((void**)&dir, dir_words * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&caps, dir_words * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&settle_bits, settle_words * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&settle_list, (uint64_t)SETTLE_CAP * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&sums, (uint64_t)n_chunks * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_meta, 64);
-  if (e != hipSuccess) return bail(KM_E_NOMEM, "hipMalloc failed", e);
+  int rc = dir.alloc(dir_words);
+  if (rc == KM_OK) rc = caps.alloc(dir_words);
+  if (rc == KM_OK) rc = settle_bits.alloc(settle_words);
+  if (rc == KM_OK) rc = settle_list.alloc(SETTLE_CAP);
+  if (rc == KM_OK) rc = sums.alloc(n_chunks);
+  if (rc == KM_OK) rc = d_meta.alloc(8);
+  if (rc != KM_OK) return rc;
   (void)hipMemsetAsync(dir, 0, dir_words * 4, st);
   (void)hipMemsetAsync(caps, 0, dir_words * 4, st);
   (void)hipMemsetAsync(d_meta, 0, 64, st);
 
-  kmjf shape;               // a view with the geometry only, for the build kernels
-  shape.k = h->k; shape.canonical = h->canonical;
-  shape.d_dir = dir; shape.n_buckets = n_buckets; shape.unit = unit;
-  TableView tv = view_of(&shape);
-  shape.d_dir = nullptr;    // not owned
+  const TableView tv = table_shape(h->k, h->canonical, n_buckets, unit, dir);
 
   if (n) {
     hipLaunchKernelGGL(k_count_big, dim3(grid_for(n, 256)), dim3(256), 0, st, d_counts, n, d_meta + 4);
@@ -362,9 +408,8 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
   uint64_t n_slots = 0;
   uint32_t max_probe = 2;
   int rounds = 0, dry_rounds = 0;
-  uint32_t* ctr = nullptr;          // dry rounds: entries per home pair, one byte each
-  uint64_t ctr_cap = 0;
-  ctr_ptr = &ctr;
+  DevBuf<uint32_t> ctr;             // dry rounds: entries per home pair, one byte each
+  hipError_t e;
   for (;; ++rounds) {
     const int final_round = rounds >= MAX_ROUNDS;
     (void)hipMemsetAsync(d_meta, 0, 32, st);          // [0..3]
@@ -376,26 +421,23 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
     hipLaunchKernelGGL(k_scan_apply, dim3(n_chunks), dim3(SCAN_THREADS), 0, st, dir, sums);
     e = hipMemcpyAsync(meta, d_meta, 48, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return bail(KM_E_HIP, "directory pass failed", e);
+    if (e != hipSuccess) return fail_hip(KM_E_HIP, "directory pass failed", e);
     if (meta[5] >= (1ull << 32))
-      return bail(KM_E_CAPACITY, "table needs more than 2^33 slots (32-bit directory)", hipSuccess);
+      return fail_hip(KM_E_CAPACITY, "table needs more than 2^33 slots (32-bit directory)", hipSuccess);
     n_slots = std::max<uint64_t>(64, 2ull * meta[5]);
     if (n && dry_rounds < (int)CAP_MAX_GEN) {
       // dry round (cheap: one byte per pair instead of the slots): find the buckets to double
       const uint64_t words = meta[5] / 4 + 2;
-      if (words > ctr_cap) {
-        if (ctr) (void)hipFree(ctr);
-        ctr = nullptr;
-        ctr_cap = words + words / 2;
-        e = hipMalloc((void**)&ctr, ctr_cap * 4);
-        if (e != hipSuccess) return bail(KM_E_NOMEM, "hipMalloc failed", e);
+      if (words > ctr.n) {
+        rc = ctr.alloc(words + words / 2);
+        if (rc != KM_OK) return rc;
       }
       (void)hipMemsetAsync(ctr, 0, words * 4, st);
       hipLaunchKernelGGL(k_table_dry, dim3(grid_for(n, 256)), dim3(256), 0, st, tv, d_keys, d_counts, n, caps,
                          ctr, d_meta);
       e = hipMemcpyAsync(meta, d_meta, 32, hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (e != hipSuccess) return bail(KM_E_HIP, "table build failed", e);
+      if (e != hipSuccess) return fail_hip(KM_E_HIP, "table build failed", e);
       ++dry_rounds;
       if (getenv("KM_BUILD_VERBOSE"))
         fprintf(stderr, "libkmgpu: dry round %d: %llu slots, %llu buckets to grow\n", dry_rounds,
@@ -407,12 +449,9 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
       }
       dry_rounds = (int)CAP_MAX_GEN;               // nothing to grow: go straight to the insert
     }
-    if (n_slots > slots_cap) {
-      if (slots) (void)hipFree(slots);
-      slots = nullptr;
-      slots_cap = n_slots + n_slots / 4;              // head room for the following rounds
-      e = hipMalloc((void**)&slots, (slots_cap + 16) * sizeof(Slot));
-      if (e != hipSuccess) return bail(KM_E_NOMEM, "hipMalloc failed", e);
+    if (n_slots + 16 > slots.n) {
+      rc = slots.alloc(n_slots + n_slots / 4 + 16);   // head room for the following rounds
+      if (rc != KM_OK) return rc;
     }
     hipLaunchKernelGGL(k_table_init, dim3(grid_for(n_slots, 256)), dim3(256), 0, st, slots, n_slots);
     (void)hipMemsetAsync(settle_bits, 0, settle_words * 4, st);
@@ -422,8 +461,8 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
                          d_counts, n, caps, final_round, d_meta, settle_bits, settle_list, SETTLE_CAP);
     e = hipMemcpyAsync(meta, d_meta, 64, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return bail(KM_E_HIP, "table build failed", e);
-    if (meta[1] & 0xFFFFFFFFull) return bail(KM_E_HIP, "table build overflowed", hipSuccess);
+    if (e != hipSuccess) return fail_hip(KM_E_HIP, "table build failed", e);
+    if (meta[1] & 0xFFFFFFFFull) return fail_hip(KM_E_HIP, "table build overflowed", hipSuccess);
     max_probe = std::max<uint32_t>(2, (uint32_t)meta[3] + 1);
     // ---- settle: the buckets in which the race of the insert decided who sits where are laid out again as a
     // function of their keys alone (k_table_settle); that layout also decides which of them double once more
@@ -432,7 +471,7 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
       const uint32_t lds = 128u << 10;
       // (per device and cheap: set on every build rather than remembered per process)
       e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_table_settle), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return bail(KM_E_HIP, "table settle pass: 128 KB of dynamic LDS refused", e);
+      if (e != hipSuccess) return fail_hip(KM_E_HIP, "table settle pass: 128 KB of dynamic LDS refused", e);
       const uint32_t race_probe = max_probe;
       const unsigned long long n_slots_total = meta[5];
       (void)hipMemsetAsync(d_meta + 3, 0, 8, st);
@@ -443,7 +482,7 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
       e = hipGetLastError();
       if (e == hipSuccess) e = hipMemcpyAsync(meta, d_meta, 64, hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (e != hipSuccess) return bail(KM_E_HIP, "table settle pass failed", e);
+      if (e != hipSuccess) return fail_hip(KM_E_HIP, "table settle pass failed", e);
       max_probe = std::max<uint32_t>(2, (uint32_t)meta[3] + 1);
       if (getenv("KM_BUILD_VERBOSE"))
         fprintf(stderr, "libkmgpu: settle pass: %u buckets laid out again by their keys alone (%llu too large: measured only); "
@@ -465,8 +504,8 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
   const uint64_t n_big = meta[4];
   const uint64_t n_ovf = n_big ? (n_big * 2 + 64) : 0;
   if (n_ovf) {
-    e = hipMalloc((void**)&ovf, n_ovf * sizeof(OvfSlot));
-    if (e != hipSuccess) return bail(KM_E_NOMEM, "hipMalloc failed", e);
+    rc = ovf.alloc(n_ovf);
+    if (rc != KM_OK) return rc;
     (void)hipMemsetAsync(ovf, 0, n_ovf * sizeof(OvfSlot), st);
     (void)hipMemsetAsync(d_meta + 1, 0, 8, st);
     hipLaunchKernelGGL(k_ovf_insert, dim3(grid_for(n, 256)), dim3(256), 0, st, d_keys, d_counts, n, h->k,
@@ -474,21 +513,15 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
     unsigned long long err = 0;
     e = hipMemcpyAsync(&err, d_meta + 1, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return bail(KM_E_HIP, "side table build failed", e);
-    if (err & 0xFFFFFFFFull) return bail(KM_E_HIP, "side table overflowed", hipSuccess);
+    if (e != hipSuccess) return fail_hip(KM_E_HIP, "side table build failed", e);
+    if (err & 0xFFFFFFFFull) return fail_hip(KM_E_HIP, "side table overflowed", hipSuccess);
   }
-  (void)hipFree(caps);
-  (void)hipFree(settle_bits);
-  (void)hipFree(settle_list);
-  (void)hipFree(sums);
-  (void)hipFree(d_meta);
-  if (ctr) (void)hipFree(ctr);
-  h->d_slots = slots;
-  h->d_dir = dir;
+  h->d_slots = std::move(slots);
+  h->d_dir = std::move(dir);
   h->n_buckets = n_buckets;
   h->unit = unit;
   h->max_probe = max_probe;
-  h->d_ovf = ovf;
+  h->d_ovf = std::move(ovf);
   h->n_ovf = n_ovf;
   h->n_slots = n_slots;
   h->n_groups = meta[0];
@@ -501,23 +534,17 @@ extern "C" int kmjf_upload(kmjf_t* h, int device) {
   if (!h) return fail(KM_E_ARG, "null argument");
   HIPCHK(hipSetDevice(device));
   const uint64_t n = h->keys.size();
-  uint64_t* d_keys = nullptr;
-  uint32_t* d_counts = nullptr;
+  DevBuf<uint64_t> d_keys;
+  DevBuf<uint32_t> d_counts;
   if (n) {
-    HIPCHK(hipMalloc((void**)&d_keys, n * 8));
-    hipError_t e = hipMalloc((void**)&d_counts, n * 4);
-    if (e != hipSuccess) { (void)hipFree(d_keys); return fail(KM_E_NOMEM, "hipMalloc failed"); }
-    e = hipMemcpy(d_keys, h->keys.data(), n * 8, hipMemcpyHostToDevice);
+    int rc = d_keys.alloc(n);
+    if (rc == KM_OK) rc = d_counts.alloc(n);
+    if (rc != KM_OK) return rc;
+    hipError_t e = hipMemcpy(d_keys, h->keys.data(), n * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_counts, h->counts.data(), n * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(d_keys); (void)hipFree(d_counts);
-      return fail(KM_E_HIP, "record upload failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(KM_E_HIP, "record upload failed: %s", hipGetErrorString(e));
   }
-  int rc = kmjf_upload_from_device(h, device, d_keys, d_counts, n, nullptr);
-  if (d_keys) (void)hipFree(d_keys);
-  if (d_counts) (void)hipFree(d_counts);
-  return rc;
+  return kmjf_upload_from_device(h, device, d_keys, d_counts, n, nullptr);
 }
 
 // ---- kmjf_broadcast: one process, several GPUs.  RCCL is looked up at run time (dlopen) so that the library
@@ -571,72 +598,75 @@ extern "C" int kmjf_broadcast(kmjf_t* h, const int* devices, int n, kmjf_t** rep
     return rc;
   }
   const RcclApi* api = rccl_api();
-  if (!api) return fail(KM_E_HIP, "RCCL (librccl.so.1) cannot be loaded: %s", dlerror() ? dlerror() : "symbols missing");
+  if (!api) {
+    const char* why = dlerror();                       // (a second call returns NULL)
+    return fail(KM_E_HIP, "RCCL (librccl.so.1) cannot be loaded: %s", why ? why : "symbols missing");
+  }
   const uint64_t cnt = h->keys.size();
   const uint64_t bytes = cnt * 12;                     // keys, then counts: one buffer, one broadcast
-  std::vector<unsigned char*> buf(n, nullptr);
-  std::vector<hipStream_t> st(n, nullptr);
-  std::vector<ncclComm_t> comm(n, nullptr);
-  std::vector<kmjf_t*> made;
-  bool comms_up = false;
-  auto cleanup = [&]() {
-    for (int i = 0; i < n; ++i) {
-      (void)hipSetDevice(devices[i]);
-      if (buf[i]) (void)hipFree(buf[i]);
-      if (st[i]) (void)hipStreamDestroy(st[i]);
-      if (comms_up && comm[i]) (void)api->CommDestroy(comm[i]);
+  struct Peer {                                        // one device's share, released under that device
+    int device = 0;
+    unsigned char* buf = nullptr;
+    hipStream_t st = nullptr;
+    ncclComm_t comm = nullptr;
+    const RcclApi* api = nullptr;                      // set once the communicators are up
+    Peer() = default;
+    Peer(const Peer&) = delete;
+    ~Peer() {
+      (void)hipSetDevice(device);
+      if (buf) (void)hipFree(buf);
+      if (st) (void)hipStreamDestroy(st);
+      if (api && comm) (void)api->CommDestroy(comm);
     }
   };
-  auto bail = [&](int code, const char* what, const char* detail) {
-    cleanup();
-    for (kmjf_t* r : made) (void)kmjf_close(r);
-    for (int i = 0; i < n; ++i) replicas[i] = nullptr;
-    return fail(code, "%s: %s", what, detail);
-  };
+  std::vector<std::unique_ptr<kmjf>> made(n);         // the tables of devices[1..]: handed out once all are built
+  std::vector<Peer> peer(n);
+  for (int i = 0; i < n; ++i) peer[i].device = devices[i];
   for (int i = 0; i < n; ++i) {
     hipError_t e = hipSetDevice(devices[i]);
-    if (e == hipSuccess) e = hipMalloc((void**)&buf[i], bytes ? bytes : 16);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking);
-    if (e != hipSuccess) return bail(KM_E_NOMEM, "record buffer", hipGetErrorString(e));
+    if (e == hipSuccess) e = hipMalloc((void**)&peer[i].buf, bytes ? bytes : 16);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&peer[i].st, hipStreamNonBlocking);
+    if (e != hipSuccess) return fail_hip(KM_E_NOMEM, "record buffer", e);
   }
   {
     hipError_t e = hipSetDevice(devices[0]);
-    if (e == hipSuccess && cnt) e = hipMemcpy(buf[0], h->keys.data(), cnt * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && cnt) e = hipMemcpy(buf[0] + cnt * 8, h->counts.data(), cnt * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return bail(KM_E_HIP, "record upload", hipGetErrorString(e));
+    if (e == hipSuccess && cnt) e = hipMemcpy(peer[0].buf, h->keys.data(), cnt * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && cnt) e = hipMemcpy(peer[0].buf + cnt * 8, h->counts.data(), cnt * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail_hip(KM_E_HIP, "record upload", e);
   }
+  std::vector<ncclComm_t> comm(n, nullptr);
   ncclResult_t nr = api->CommInitAll(comm.data(), n, devices);
-  if (nr != ncclSuccess) return bail(KM_E_HIP, "ncclCommInitAll", api->GetErrorString ? api->GetErrorString(nr) : "failed");
-  comms_up = true;
+  if (nr != ncclSuccess) return fail(KM_E_HIP, "ncclCommInitAll: %s", api->GetErrorString ? api->GetErrorString(nr) : "failed");
+  for (int i = 0; i < n; ++i) { peer[i].comm = comm[i]; peer[i].api = api; }
   if (bytes) {
     nr = api->GroupStart();
     for (int i = 0; i < n && nr == ncclSuccess; ++i) {
       (void)hipSetDevice(devices[i]);
-      nr = api->Broadcast(buf[i], buf[i], bytes, ncclUint8, 0, comm[i], st[i]);
+      nr = api->Broadcast(peer[i].buf, peer[i].buf, bytes, ncclUint8, 0, peer[i].comm, peer[i].st);
     }
     const ncclResult_t ne = api->GroupEnd();
     if (nr == ncclSuccess) nr = ne;
-    if (nr != ncclSuccess) return bail(KM_E_HIP, "ncclBroadcast", api->GetErrorString ? api->GetErrorString(nr) : "failed");
+    if (nr != ncclSuccess) return fail(KM_E_HIP, "ncclBroadcast: %s", api->GetErrorString ? api->GetErrorString(nr) : "failed");
   }
   for (int i = 0; i < n; ++i) {
     hipError_t e = hipSetDevice(devices[i]);
-    if (e == hipSuccess) e = hipStreamSynchronize(st[i]);
-    if (e != hipSuccess) return bail(KM_E_HIP, "broadcast did not complete", hipGetErrorString(e));
+    if (e == hipSuccess) e = hipStreamSynchronize(peer[i].st);
+    if (e != hipSuccess) return fail_hip(KM_E_HIP, "broadcast did not complete", e);
   }
   // every device builds its own table from its copy of the records
   for (int i = 0; i < n; ++i) {
     kmjf_t* r = h;
     if (i > 0) {
       int rc = kmjf_create(h->k, h->canonical, &r);
-      if (rc != KM_OK) return bail(rc, "replica", km_last_error());
-      made.push_back(r);
+      if (rc != KM_OK) { const std::string why = km_last_error(); return fail(rc, "replica: %s", why.c_str()); }
+      made[i].reset(r);
     }
-    int rc = kmjf_upload_from_device(r, devices[i], reinterpret_cast<const uint64_t*>(buf[i]),
-                                     reinterpret_cast<const uint32_t*>(buf[i] + cnt * 8), cnt, st[i]);
-    if (rc != KM_OK) { const std::string why = km_last_error(); return bail(rc, "table build", why.c_str()); }
-    replicas[i] = r;
+    int rc = kmjf_upload_from_device(r, devices[i], reinterpret_cast<const uint64_t*>(peer[i].buf),
+                                     reinterpret_cast<const uint32_t*>(peer[i].buf + cnt * 8), cnt, peer[i].st);
+    if (rc != KM_OK) { const std::string why = km_last_error(); return fail(rc, "table build: %s", why.c_str()); }
   }
-  cleanup();
+  replicas[0] = h;
+  for (int i = 1; i < n; ++i) replicas[i] = made[i].release();
   return KM_OK;
 }
 
@@ -653,70 +683,59 @@ extern "C" int kmjf_load(const char* path, int device, kmjf_t** out) {
   if (rc == 1) return fail(KM_E_IO, "%s", err.c_str());
   if (rc == 2) return fail(KM_E_FORMAT, "%s", err.c_str());
   if (rc == 3) return fail(KM_E_K, "%s", err.c_str());
-  FILE* f = static_cast<FILE*>(file);
-  if (lay.k < 2 || lay.k > 32) { fclose(f); return fail(KM_E_K, "k=%d unsupported", lay.k); }
+  File f(static_cast<FILE*>(file));
+  if (lay.k < 2 || lay.k > 32) return fail(KM_E_K, "k=%d unsupported", lay.k);
   const uint64_t n = lay.n_records;
   const uint64_t rec = (uint64_t)lay.key_bytes + lay.counter_bytes;
   const uint64_t body = n * rec;
   // map the whole file (the record area does not start on a page boundary)
   const uint64_t map_len = lay.body_offset + body;
-  void* map = nullptr;
+  Mapping map(nullptr, Unmap{map_len});
   if (body) {
-    map = mmap(nullptr, map_len, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fileno(f), 0);   // populate: no per-page faults during the copy
-    if (map == MAP_FAILED) { fclose(f); return fail(KM_E_IO, "cannot map %s", path); }
-    (void)madvise(map, map_len, MADV_SEQUENTIAL);
+    void* m = mmap(nullptr, map_len, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fileno(f), 0);   // populate: no per-page faults during the copy
+    if (m == MAP_FAILED) return fail(KM_E_IO, "cannot map %s", path);
+    map.reset(m);
+    (void)madvise(m, map_len, MADV_SEQUENTIAL);
   }
-  fclose(f);                                   // the mapping stays valid
-  kmjf* h = new (std::nothrow) kmjf;
-  if (!h) { if (map) munmap(map, map_len); return fail(KM_E_NOMEM, "host allocation failed"); }
-  h->k = lay.k;
-  h->canonical = lay.canonical;
+  f.reset();                                   // the mapping stays valid
 
-  unsigned char* d_raw = nullptr;
-  uint64_t* d_keys = nullptr;
-  uint32_t* d_counts = nullptr;
-  unsigned long long* d_meta = nullptr;
-  auto cleanup = [&]() {
-    if (map) munmap(map, map_len);
-    if (d_raw) (void)hipFree(d_raw);
-    if (d_keys) (void)hipFree(d_keys);
-    if (d_counts) (void)hipFree(d_counts);
-    if (d_meta) (void)hipFree(d_meta);
-  };
-  auto bail = [&](int code, const char* what, hipError_t e) {
-    cleanup();
-    delete h;
-    return fail(code, "%s: %s", what, hipGetErrorString(e));
-  };
   hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return bail(KM_E_HIP, "device setup failed", e);
+  if (e != hipSuccess) return fail_hip(KM_E_HIP, "device setup failed", e);
   // KM_LOAD_CHUNK_KB: copy granularity (default 256 MB; tests use small chunks)
   uint64_t chunk_target = 256ull << 20;
   if (const char* ck = getenv("KM_LOAD_CHUNK_KB")) { long v = atol(ck); if (v >= 1) chunk_target = (uint64_t)v << 10; }
   const uint64_t chunk_recs = std::max<uint64_t>(1, chunk_target / rec);
-  if (n) {
-    e = hipMalloc((void**)&d_raw, std::min(n, chunk_recs) * rec);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_keys, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_counts, n * 4);
-  }
-  if (e == hipSuccess) e = hipMalloc((void**)&d_meta, 8);
-  if (e != hipSuccess) return bail(KM_E_NOMEM, "allocation failed", e);
-  (void)hipMemset(d_meta, 0, 8);
-  const unsigned char* src = static_cast<const unsigned char*>(map) + lay.body_offset;
-  for (uint64_t done = 0; done < n;) {
-    const uint64_t m = std::min(chunk_recs, n - done);
-    e = hipMemcpy(d_raw, src + done * rec, m * rec, hipMemcpyHostToDevice);   // pageable: staged by the runtime
-    if (e != hipSuccess) return bail(KM_E_HIP, "ingestion failed", e);
-    hipLaunchKernelGGL(k_unpack_records, dim3(grid_for(m, 256)), dim3(256), 0, nullptr, d_raw, m, lay.key_bytes,
-                       lay.counter_bytes, d_keys + done, d_counts + done, d_meta);
-    done += m;
-  }
+  DevBuf<uint64_t> d_keys;
+  DevBuf<uint32_t> d_counts;
+  DevBuf<unsigned long long> d_meta;
   unsigned long long nz = 0;
-  e = hipMemcpy(&nz, d_meta, 8, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return bail(KM_E_HIP, "ingestion failed", e);
-  if (d_raw) { (void)hipFree(d_raw); d_raw = nullptr; }
+  {
+    DevBuf<unsigned char> d_raw;               // one chunk of the records as stored: freed before the table build
+    if (n) {
+      rc = d_raw.alloc(std::min(n, chunk_recs) * rec);
+      if (rc == KM_OK) rc = d_keys.alloc(n);
+      if (rc == KM_OK) rc = d_counts.alloc(n);
+    }
+    if (rc == KM_OK) rc = d_meta.alloc(1);
+    if (rc != KM_OK) return rc;
+    (void)hipMemset(d_meta, 0, 8);
+    const unsigned char* src = static_cast<const unsigned char*>(map.get()) + lay.body_offset;
+    for (uint64_t done = 0; done < n;) {
+      const uint64_t m = std::min(chunk_recs, n - done);
+      e = hipMemcpy(d_raw, src + done * rec, m * rec, hipMemcpyHostToDevice);   // pageable: staged by the runtime
+      if (e != hipSuccess) return fail_hip(KM_E_HIP, "ingestion failed", e);
+      hipLaunchKernelGGL(k_unpack_records, dim3(grid_for(m, 256)), dim3(256), 0, nullptr, d_raw, m, lay.key_bytes,
+                         lay.counter_bytes, d_keys + done, d_counts + done, d_meta);
+      done += m;
+    }
+    e = hipMemcpy(&nz, d_meta, 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip(KM_E_HIP, "ingestion failed", e);
+  }
+  kmjf* h = new (std::nothrow) kmjf;
+  if (!h) return fail(KM_E_NOMEM, "host allocation failed");
+  h->k = lay.k;
+  h->canonical = lay.canonical;
   rc = kmjf_upload_from_device(h, device, d_keys, d_counts, n, nullptr);
-  cleanup();
   if (rc != KM_OK) { delete h; return rc; }
   h->n_records = nz;
   *out = h;
@@ -754,18 +773,16 @@ extern "C" int kmjf_query_batch(kmjf_t* h, const uint64_t* kmers, uint64_t n, ui
   if (!h->d_slots) return fail(KM_E_STATE, "table not uploaded");
   if (!n) return KM_OK;
   HIPCHK(hipSetDevice(h->device));
-  uint64_t* dk = nullptr;
-  uint32_t* dc = nullptr;
-  HIPCHK(hipMalloc((void**)&dk, n * 8));
-  hipError_t e = hipMalloc((void**)&dc, n * 4);
-  if (e != hipSuccess) { (void)hipFree(dk); return fail(KM_E_NOMEM, "hipMalloc failed"); }
-  int rc = KM_OK;
-  e = hipMemcpy(dk, kmers, n * 8, hipMemcpyHostToDevice);
+  DevBuf<uint64_t> dk;
+  DevBuf<uint32_t> dc;
+  int rc = dk.alloc(n);
+  if (rc == KM_OK) rc = dc.alloc(n);
+  if (rc != KM_OK) return rc;
+  hipError_t e = hipMemcpy(dk, kmers, n * 8, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     rc = kmjf_query_batch_dev(h, dk, n, dc, nullptr);
     if (rc == KM_OK) e = hipMemcpy(counts, dc, n * 4, hipMemcpyDeviceToHost);
   }
-  (void)hipFree(dk); (void)hipFree(dc);
   if (rc != KM_OK) return rc;
   if (e != hipSuccess) return fail(KM_E_HIP, "query batch failed: %s", hipGetErrorString(e));
   return KM_OK;
@@ -777,22 +794,21 @@ extern "C" int kmjf_children_batch(kmjf_t* h, const uint64_t* kmers, uint64_t n,
   if (!h->d_slots) return fail(KM_E_STATE, "table not uploaded");
   if (!n) return KM_OK;
   HIPCHK(hipSetDevice(h->device));
-  uint64_t* dk = nullptr;
-  uint8_t* dm = nullptr;
-  uint32_t* dc = nullptr;
-  HIPCHK(hipMalloc((void**)&dk, n * 8));
-  hipError_t e = hipMalloc((void**)&dm, n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dc, n * 16);
-  int rc = KM_OK;
-  if (e == hipSuccess) e = hipMemcpy(dk, kmers, n * 8, hipMemcpyHostToDevice);
+  DevBuf<uint64_t> dk;
+  DevBuf<uint8_t> dm;
+  DevBuf<uint32_t> dc;
+  int rc = dk.alloc(n);
+  if (rc != KM_OK) return rc;
+  if (dm.alloc(n) != KM_OK || dc.alloc(4 * n) != KM_OK) {
+    const std::string why = km_last_error();
+    return fail(KM_E_HIP, "children batch failed: %s", why.c_str());
+  }
+  hipError_t e = hipMemcpy(dk, kmers, n * 8, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     rc = kmjf_children_batch_dev(h, dk, n, ratio, n_cutoff, forward, dm, dc, nullptr);
     if (rc == KM_OK && mask) e = hipMemcpy(mask, dm, n, hipMemcpyDeviceToHost);
     if (rc == KM_OK && e == hipSuccess && counts4) e = hipMemcpy(counts4, dc, n * 16, hipMemcpyDeviceToHost);
   }
-  (void)hipFree(dk);
-  if (dm) (void)hipFree(dm);
-  if (dc) (void)hipFree(dc);
   if (rc != KM_OK) return rc;
   if (e != hipSuccess) return fail(KM_E_HIP, "children batch failed: %s", hipGetErrorString(e));
   return KM_OK;
@@ -848,23 +864,6 @@ const Knobs& knobs() {
 
 // ---------------------------------------------------------------------------- batch
 namespace {
-
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  uint64_t n = 0;
-  int alloc(uint64_t count) {
-    if (count <= n && p) return KM_OK;
-    release();
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-    if (e != hipSuccess) { p = nullptr; n = 0; return fail(KM_E_NOMEM, "hipMalloc of %llu bytes failed",
-                                                          (unsigned long long)(count * sizeof(T))); }
-    n = count;
-    return KM_OK;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
 
 constexpr uint32_t FAST_EXTRA = 160;          // walk-discovered nodes a fast-tier target may add
 constexpr uint32_t FAST_LDS_LIMIT = 64 * 1024;
@@ -940,8 +939,8 @@ struct km_batch {
   uint32_t pure_lds = 0;
   bool timed = false;                  // the last run recorded its timing events
   bool timed_fine = false;             // ... those between the kernels of the walk stage as well
-  hipGraph_t graph = nullptr;          // captured step (KM_RUN_HIPGRAPH)
-  hipGraphExec_t gexec = nullptr;
+  Graph graph;                         // captured step (KM_RUN_HIPGRAPH)
+  GraphExec gexec;
   int graph_stages = 0;
   hipStream_t graph_stream = nullptr;
   DevBuf<uint64_t> d_probes, d_fetches;
@@ -958,10 +957,10 @@ struct km_batch {
   DevBuf<unsigned long long> d_loc, d_blk_tot, d_blk_base, d_psort;
   DevBuf<unsigned int> d_scan_ticket;
   DevBuf<uint32_t> d_cnt4;
-  unsigned char* d_out = nullptr;
-  unsigned char* h_out = nullptr;
+  DevBuf<unsigned char> d_out;
+  Pinned h_out;
   uint64_t out_cap = 0;
-  hipEvent_t ev_out = nullptr;
+  Event ev_out;
   bool deliver_pending = false, result_ready = false;
   bool lean = false;                  // the pending / ready delivery omits bare-reference node counts
   bool count16 = false;               // ... and carries 16-bit counts + escape list (KM_DELIVER_COUNT16)
@@ -1004,9 +1003,15 @@ struct km_batch {
   GraphArgs ga{};
   uint32_t walk_lds = 0, graph_lds = 0;
   // timing
-  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  Event ev[7];
   float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool timed_deliver = false;
+
+  ~km_batch() { drop_graph(); }              // the captured step goes before the buffers it uses
+  void drop_graph() {
+    gexec.reset();
+    graph.reset();
+  }
 };
 
 static uint64_t default_tail_bytes(const km_batch* b, uint64_t nodes, uint64_t extra) {
@@ -1018,13 +1023,12 @@ static uint64_t default_tail_bytes(const km_batch* b, uint64_t nodes, uint64_t e
 static int ensure_out(km_batch* b, uint64_t tail_need) {
   const uint64_t need = out_layout(b->max_targets).a_bytes + tail_need;
   if (b->d_out && b->h_out && need <= b->out_cap) return KM_OK;
-  if (b->d_out) (void)hipFree(b->d_out);
-  if (b->h_out) (void)hipHostFree(b->h_out);
-  b->d_out = nullptr; b->h_out = nullptr; b->out_cap = 0;
+  b->h_out.reset();
+  b->out_cap = 0;
   const uint64_t cap = need + need / 8;
-  if (hipMalloc((void**)&b->d_out, cap) != hipSuccess) { b->d_out = nullptr; return fail(KM_E_NOMEM, "hipMalloc of the delivery buffer failed"); }
-  if (hipHostMalloc((void**)&b->h_out, cap, hipHostMallocDefault) != hipSuccess) {
-    b->h_out = nullptr;
+  if (b->d_out.alloc(cap) != KM_OK) return fail(KM_E_NOMEM, "hipMalloc of the delivery buffer failed");
+  if (hipHostMalloc((void**)&b->h_out.h, cap, hipHostMallocDefault) != hipSuccess) {
+    b->h_out.h = nullptr;
     return fail(KM_E_NOMEM, "pinned allocation of %llu bytes failed", (unsigned long long)cap);
   }
   b->out_cap = cap;
@@ -1118,49 +1122,22 @@ extern "C" int km_batch_create(kmjf_t* h, const km_params_t* params, uint32_t ma
   // the walk rarely adds more than a few nodes per target: the tail grows on demand
   if (rc == KM_OK) rc = ensure_out(b, default_tail_bytes(b, max_total_bases + 16ull * max_targets, 16ull * max_targets));
   if (rc == KM_OK) {
-    if (hipEventCreateWithFlags(&b->ev_out, hipEventDisableTiming) != hipSuccess)
+    if (hipEventCreateWithFlags(&b->ev_out.h, hipEventDisableTiming) != hipSuccess)
       rc = fail(KM_E_HIP, "stream/event creation failed");
   }
   if (rc == KM_OK) {
     for (int i = 0; i < 7; ++i)
-      if (hipEventCreate(&b->ev[i]) != hipSuccess) rc = fail(KM_E_HIP, "hipEventCreate failed");
+      if (hipEventCreate(&b->ev[i].h) != hipSuccess) rc = fail(KM_E_HIP, "hipEventCreate failed");
   }
-  if (rc != KM_OK) { km_batch_destroy(b); return rc; }
+  if (rc != KM_OK) { delete b; return rc; }
   *out = b;
   return KM_OK;
-}
-
-static void drop_graph(km_batch* b) {
-  if (b->gexec) (void)hipGraphExecDestroy(b->gexec);
-  if (b->graph) (void)hipGraphDestroy(b->graph);
-  b->gexec = nullptr;
-  b->graph = nullptr;
 }
 
 extern "C" int km_batch_destroy(km_batch_t* b) {
   if (!b) return KM_OK;
   (void)hipSetDevice(b->device);
   (void)hipDeviceSynchronize();
-  drop_graph(b);
-  b->d_bases.release(); b->d_toff.release(); b->d_woff.release(); b->d_packed.release();
-  b->d_items.release(); b->d_item_off.release(); b->d_flagbits.release(); b->d_fw_off.release();
-  b->d_tflag.release(); b->d_flagged.release(); b->d_flag_rec.release(); b->d_left.release(); b->d_epi.release(); b->d_nflagged.release(); b->d_dfs_probes.release();
-  b->d_node_base.release(); b->d_node_cap.release();
-  b->d_n_nodes.release(); b->d_n_ref.release(); b->d_status.release(); b->d_gstatus.release();
-  b->d_npaths.release(); b->d_pathbase.release(); b->d_need_full.release(); b->d_t_nruns.release(); b->d_t_refmax.release();
-  b->d_loc.release(); b->d_cnt4.release(); b->d_blk_tot.release(); b->d_blk_base.release(); b->d_scan_ticket.release(); b->d_psort.release();
-  if (b->ev_out) (void)hipEventDestroy(b->ev_out);
-  b->d_probes.release(); b->d_fetches.release();
-  b->d_node_kmer.release(); b->d_node_cnt.release(); b->d_counters.release();
-  b->d_p_target.release(); b->d_p_runbase.release(); b->d_p_nruns.release(); b->d_p_len.release();
-  b->d_p_mincov.release(); b->d_r_start.release(); b->d_r_len.release();
-  b->d_big_ids.release(); b->d_big_ws.release(); b->d_tref.release(); b->d_frames.release(); b->d_stamps.release();
-  b->d_node_base0.release(); b->d_big_ctl.release(); b->d_big_walk.release(); b->d_big_graph.release();
-  b->d_bigdev_walk_ws.release(); b->d_bigdev_graph_ws.release();
-  b->d_t_eremoved.release(); b->d_t_enonref.release(); b->d_loop_list.release(); b->d_loop_ctl.release();
-  for (int i = 0; i < 7; ++i) if (b->ev[i]) (void)hipEventDestroy(b->ev[i]);
-  if (b->d_out) (void)hipFree(b->d_out);
-  if (b->h_out) (void)hipHostFree(b->h_out);
   delete b;
   return KM_OK;
 }
@@ -1231,7 +1208,7 @@ static int layout_targets(km_batch* b, const uint64_t* offsets, uint32_t n) {
 
 static int push_layout(km_batch* b, hipStream_t st) {
   const uint32_t n = b->n_targets;
-  drop_graph(b);                       // geometry and pointers may change with the targets
+  b->drop_graph();                     // geometry and pointers may change with the targets
   {
     // tref[j] = distance of reference node j from the source along the reference chain,
     // accumulated exactly as Graph.py does: float32 0 + 0.01f, then + 0.01f per hop
@@ -1536,8 +1513,8 @@ static int enqueue_deliver(km_batch* b, hipStream_t st, bool lean, bool count16 
   b->result_ready = false;
   if (n == 0) {
     memset(b->h_out, 0, L.a_bytes + 64);
-    reinterpret_cast<unsigned long long*>(b->h_out)[OT_TAIL_BYTES] = 16;
-    reinterpret_cast<unsigned long long*>(b->h_out)[OT_SERIAL] = ++b->serial;
+    reinterpret_cast<unsigned long long*>(b->h_out.h)[OT_TAIL_BYTES] = 16;
+    reinterpret_cast<unsigned long long*>(b->h_out.h)[OT_SERIAL] = ++b->serial;
     b->copied_tail = 16;
     b->deliver_pending = true;
     HIPCHK(hipEventRecord(b->ev_out, st));
@@ -1614,7 +1591,7 @@ static int enqueue_deliver(km_batch* b, hipStream_t st, bool lean, bool count16 
 static int restore_layout(km_batch* b, hipStream_t st) {
   (void)st;
   if (!b->layout_moved) return KM_OK;
-  drop_graph(b);
+  b->drop_graph();
   b->h_node_base = b->h_node_base0;
   b->h_node_cap = b->h_node_cap0;
   b->node_pool_used = b->node_pool0;
@@ -1695,7 +1672,7 @@ extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
   const bool capturing = want_graph && st != nullptr && (stages & KM_STAGE_WALK);   // the NULL stream cannot be captured
   if (capturing) {
     b->timed = false;
-    drop_graph(b);
+    b->drop_graph();
     HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
   }
   ht[2] = host_trace ? host_now_us() : 0;
@@ -1772,8 +1749,8 @@ extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
   b->ran_graph = true;                      // graph_mode says how far it went
   if (b->timed) HIPCHK(hipEventRecord(b->ev[2], st));
   if (capturing) {
-    HIPCHK(hipStreamEndCapture(st, &b->graph));
-    HIPCHK(hipGraphInstantiate(&b->gexec, b->graph, nullptr, nullptr, 0));
+    HIPCHK(hipStreamEndCapture(st, &b->graph.h));
+    HIPCHK(hipGraphInstantiate(&b->gexec.h, b->graph, nullptr, nullptr, 0));
     b->graph_stages = stages;
     b->graph_stream = st;
     HIPCHK(hipGraphLaunch(b->gexec, st));
@@ -1875,7 +1852,7 @@ static int launch_big_graph_dev(km_batch* b, hipStream_t st) {
 static int run_big_walk(km_batch* b, const std::vector<uint32_t>& ids, hipStream_t st) {
   const uint32_t nb = (uint32_t)ids.size();
   const int k = b->db->k;
-  drop_graph(b);                      // a captured step holds the addresses that change below
+  b->drop_graph();                    // a captured step holds the addresses that change below
   b->layout_moved = true;
   if (b->big_entry) {                 // the device's own large tier may have re-homed targets of this run
     HIPCHK(hipMemcpyAsync(b->h_node_base.data(), b->d_node_base.p, (uint64_t)b->n_targets * 8, hipMemcpyDeviceToHost, st));
@@ -1897,15 +1874,14 @@ static int run_big_walk(km_batch* b, const std::vector<uint32_t>& ids, hipStream
   }
   const uint64_t need = b->node_pool_used + extra;
   if (need > b->d_node_kmer.n) {
-    // grow the pools, keeping the fast-tier results
+    // grow the pools, keeping the fast-tier results (the old pools go right after the copy)
     DevBuf<uint64_t> nk; DevBuf<uint32_t> nc;
     int rc = nk.alloc(need); if (rc != KM_OK) return rc;
-    rc = nc.alloc(need); if (rc != KM_OK) { nk.release(); return rc; }
+    rc = nc.alloc(need); if (rc != KM_OK) return rc;
     HIPCHK(hipMemcpyAsync(nk.p, b->d_node_kmer.p, b->node_pool_used * 8, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(nc.p, b->d_node_cnt.p, b->node_pool_used * 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
-    b->d_node_kmer.release(); b->d_node_cnt.release();
-    b->d_node_kmer = nk; b->d_node_cnt = nc;
+    b->d_node_kmer = std::move(nk); b->d_node_cnt = std::move(nc);
   }
   b->node_pool_used = need;
   // the seed kernel's results (the counts of the target's own k-mers) move to the new storage
@@ -1970,7 +1946,7 @@ static int run_big_graph(km_batch* b, const std::vector<uint32_t>& ids, hipStrea
 }
 
 static int grow_path_pools(km_batch* b) {
-  drop_graph(b);                      // a captured step holds the old pool addresses and sizes
+  b->drop_graph();                    // a captured step holds the old pool addresses and sizes
   b->path_pool = (b->path_pool * 4 / POOL_GROUPS + 1) * POOL_GROUPS;
   b->run_pool = (b->run_pool * 4 / POOL_GROUPS + 1) * POOL_GROUPS;
   int rc = KM_OK;
@@ -2029,7 +2005,7 @@ extern "C" int km_batch_sync(km_batch_t* b) {
   std::vector<uint32_t> big;
   for (uint32_t t = 0; t < n; ++t) if (b->h_status[t] == T_NEEDS_BIG) big.push_back(t);
   b->n_big = (uint32_t)big.size();
-  if (b->big_entry && !big.empty() && !b->bigdev_armed) { b->bigdev_armed = true; drop_graph(b); }
+  if (b->big_entry && !big.empty() && !b->bigdev_armed) { b->bigdev_armed = true; b->drop_graph(); }
   std::vector<char> force_big(n, 0);
   bool changed = false;
   if (!big.empty()) {
@@ -2117,18 +2093,18 @@ static int finish_result(km_batch* b, bool need_full) {
     const unsigned long long nh = T[OT_NEEDS_HOST];
     {
       const uint32_t fl = (uint32_t)std::min<unsigned long long>(T[OT_N_FLAGGED], 0x7FFFFFFFull);
-      if (b->gexec && b->flagged_seen != 0xFFFFFFFFu && (fl > b->flagged_seen + b->flagged_seen / 8 + 32 || 4 * fl + 256 < b->flagged_seen)) drop_graph(b);
+      if (b->gexec && b->flagged_seen != 0xFFFFFFFFu && (fl > b->flagged_seen + b->flagged_seen / 8 + 32 || 4 * fl + 256 < b->flagged_seen)) b->drop_graph();
       b->flagged_seen = fl;
     }
     if (b->ran_graph && b->graph_mode == 0) {
       const uint32_t seen = (uint32_t)std::min<unsigned long long>(T[OT_N_GRAPH_LIST], 0x7FFFFFFFull);
       // (a captured step holds its grid: it is dropped when the list outgrows a quarter of it or shrinks to a 16th)
-      if (b->gexec && b->graph_list_seen != 0xFFFFFFFFu && (seen > 2 * b->graph_list_seen + 16 || 16 * seen + 64 < b->graph_list_seen)) drop_graph(b);
+      if (b->gexec && b->graph_list_seen != 0xFFFFFFFFu && (seen > 2 * b->graph_list_seen + 16 || 16 * seen + 64 < b->graph_list_seen)) b->drop_graph();
       b->graph_list_seen = seen;
     }
     if (b->big_entry && !b->bigdev_armed && ((nh & 1ull) || T[OT_N_BIG_DEV])) {
       b->bigdev_armed = true;              // from the next run on, the device's own large tier is launched
-      drop_graph(b);                       // (a captured step does not contain its launches)
+      b->drop_graph();                     // (a captured step does not contain its launches)
     }
     if (!nh && b->count16 && T[OT_N_ESC] > OUT_ESC_CAP) {
       // more counts >= 65535 than the escape list holds: this batch is delivered with 32-bit counts
@@ -2280,12 +2256,11 @@ extern "C" int km_device_sync(int device) {
 extern "C" int km_device_copy_GBs(int device, uint64_t bytes, int reps, double* gbs) {
   if (!gbs || !bytes || reps < 1) return fail(KM_E_ARG, "bad argument");
   HIPCHK(hipSetDevice(device));
-  void *a = nullptr, *b = nullptr;
-  if (hipMalloc(&a, bytes) != hipSuccess) return fail(KM_E_NOMEM, "hipMalloc failed");
-  if (hipMalloc(&b, bytes) != hipSuccess) { (void)hipFree(a); return fail(KM_E_NOMEM, "hipMalloc failed"); }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipEventCreate(&e0);
-  if (e == hipSuccess) e = hipEventCreate(&e1);
+  DevBuf<unsigned char> a, b;
+  if (a.alloc(bytes) != KM_OK || b.alloc(bytes) != KM_OK) return fail(KM_E_NOMEM, "hipMalloc failed");
+  Event e0, e1;
+  hipError_t e = hipEventCreate(&e0.h);
+  if (e == hipSuccess) e = hipEventCreate(&e1.h);
   if (e == hipSuccess) e = hipMemcpy(b, a, bytes, hipMemcpyDeviceToDevice);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
@@ -2294,10 +2269,6 @@ extern "C" int km_device_copy_GBs(int device, uint64_t bytes, int reps, double* 
   if (e == hipSuccess) e = hipEventSynchronize(e1);
   float ms = 0;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(a);
-  (void)hipFree(b);
   if (e != hipSuccess) return fail(KM_E_HIP, "copy bandwidth measurement failed: %s", hipGetErrorString(e));
   *gbs = 2.0 * (double)reps * (double)bytes / ((double)ms * 1e-3) / 1e9;
   return KM_OK;
@@ -2310,17 +2281,17 @@ extern "C" int km_probe_bench(kmjf_t* h, const uint64_t* kmers, uint64_t n, int 
   if (!h || !kmers || !n || reps < 1 || !query_ms || !children_ms) return fail(KM_E_ARG, "bad argument");
   if (!h->d_slots) return fail(KM_E_STATE, "table not uploaded");
   HIPCHK(hipSetDevice(h->device));
-  uint64_t* dk = nullptr;
-  uint32_t* dq = nullptr;
-  uint8_t* dm = nullptr;
-  uint32_t* dc = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  DevBuf<uint64_t> dk;
+  DevBuf<uint32_t> dq, dc;
+  DevBuf<uint8_t> dm;
+  Event ev[3];
+  if (dk.alloc(n) != KM_OK || dq.alloc(n) != KM_OK || dm.alloc(n) != KM_OK || dc.alloc(4 * n) != KM_OK) {
+    const std::string why = km_last_error();
+    return fail(KM_E_HIP, "probe benchmark failed: %s", why.c_str());
+  }
   int rc = KM_OK;
-  hipError_t e = hipMalloc((void**)&dk, n * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&dq, n * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&dm, n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dc, n * 16);
-  for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i].h);
   if (e == hipSuccess) e = hipMemcpy(dk, kmers, n * 8, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     for (int w = 0; w < 2 && rc == KM_OK; ++w) {
@@ -2347,11 +2318,6 @@ extern "C" int km_probe_bench(kmjf_t* h, const uint64_t* kmers, uint64_t n, int 
       *n_zero = z;
     }
   }
-  for (int i = 0; i < 3; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
-  if (dk) (void)hipFree(dk);
-  if (dq) (void)hipFree(dq);
-  if (dm) (void)hipFree(dm);
-  if (dc) (void)hipFree(dc);
   if (rc != KM_OK) return rc;
   if (e != hipSuccess) return fail(KM_E_HIP, "probe benchmark failed: %s", hipGetErrorString(e));
   return KM_OK;
@@ -2481,17 +2447,6 @@ int32_t kmin_closed_form(uint64_t n, int32_t start, uint64_t R, uint8_t* flag) {
   if (lo > (int64_t)R + 1) return (int32_t)lo;
   return (int32_t)(*flag ? std::min<uint64_t>(R + 2, n) : R + 1);
 }
-
-struct KminDev {
-  uint8_t* text = nullptr;
-  uint64_t* stage_off = nullptr;
-  uint32_t* len = nullptr;
-  uint32_t* unit_off = nullptr;
-  unsigned long long* keys = nullptr;
-  ~KminDev() {
-    (void)hipFree(text); (void)hipFree(stage_off); (void)hipFree(len); (void)hipFree(unit_off); (void)hipFree(keys);
-  }
-};
 }  // namespace
 
 extern "C" int km_linear_kmin(int device, const uint8_t* bases, const uint64_t* base_off, uint32_t n_targets,
@@ -2538,12 +2493,18 @@ extern "C" int km_linear_kmin(int device, const uint8_t* bases, const uint64_t* 
     ~GiveBack() { if (own && !pool_give_back(st)) (void)hipStreamDestroy(st); }
   } give_back{st, own_stream};
 
-  KminDev dev;
-  HIPCHK(hipMalloc((void**)&dev.text, max_bytes + KMIN_PAD));
-  HIPCHK(hipMalloc((void**)&dev.stage_off, 8ull * max_targets));
-  HIPCHK(hipMalloc((void**)&dev.len, 4ull * max_targets));
-  HIPCHK(hipMalloc((void**)&dev.unit_off, 4ull * (max_targets + 1)));
-  HIPCHK(hipMalloc((void**)&dev.keys, 8ull * max_targets));
+  struct {
+    DevBuf<uint8_t> text;
+    DevBuf<uint64_t> stage_off;
+    DevBuf<uint32_t> len, unit_off;
+    DevBuf<unsigned long long> keys;
+  } dev;
+  int rc = dev.text.alloc(max_bytes + KMIN_PAD);
+  if (rc == KM_OK) rc = dev.stage_off.alloc(max_targets);
+  if (rc == KM_OK) rc = dev.len.alloc(max_targets);
+  if (rc == KM_OK) rc = dev.unit_off.alloc(max_targets + 1);
+  if (rc == KM_OK) rc = dev.keys.alloc(max_targets);
+  if (rc != KM_OK) return rc;
   std::vector<uint8_t> h_text;
   std::vector<uint64_t> h_off, h_keys;
   std::vector<uint32_t> h_len, h_units;

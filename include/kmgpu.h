@@ -351,6 +351,62 @@ int km_batch_debug_counts(km_batch_t* b, uint32_t* out4);
 int km_linear_kmin(int device, const uint8_t* bases, const uint64_t* base_off, uint32_t n_targets,
                    int32_t start, int32_t* kmin, int32_t* longest_repeat, uint8_t* nonexempt, void* stream);
 
+/* ---- counting k-mers from reads -----------------------------------------------------------------
+ * What `jellyfish count -m k [-C] -L lower_count -s expected_distinct` does in front of every km tool, on the
+ * GPU: reads go into a counting hash table in HBM, and km_counter_finish turns that table into an ordinary
+ * kmjf_t without the records visiting the host.  A byte of A C G T a c g t is a base, any other
+ * byte a break (N, the newline between two reads); every window of k consecutive bases is one k-mer, stored
+ * as min(key, revcomp(key)) when canonical.  Counts are exact up to 2^32 - 1; an input that repeats one k-mer
+ * more often than that is out of scope (the count wraps).  One counter lives on one device and is used from
+ * one host thread at a time; its copies and kernels run on a stream of its own. */
+typedef struct km_counter km_counter_t;
+typedef struct {
+  uint64_t bases;        /* bytes accepted as bases                                    */
+  uint64_t kmers;        /* windows counted (sum of all counts)                        */
+  uint64_t distinct;     /* occupied slots                                             */
+  uint64_t slots;        /* current capacity                                           */
+  uint32_t n_grow;       /* how often the table doubled                                */
+  uint32_t reserved;
+} km_counter_stats_t;
+/* state of the text stripper between calls: all zero before the first call of a stream */
+typedef struct {
+  int32_t  format;       /* 0 not known yet, 1 FASTA, 2 FASTQ                          */
+  int32_t  line;         /* FASTQ: line of the record the next line is (0..3)          */
+  int32_t  open;         /* FASTA: bases were written since the last break             */
+  int32_t  reserved;
+  uint64_t offset;       /* bytes consumed by the earlier calls of this stream         */
+} km_text_state_t;
+
+/* expected_distinct plays the part of Jellyfish's -s: the table starts with the next power of two at or above
+ * twice that many slots (the load limit is 1/2); 0 = a small default (65 536 slots).  The table doubles when
+ * it has to, so a wrong guess costs time, never correctness.  KM_E_K for k outside 2..32. */
+int km_counter_create(int device, int k, int canonical, uint64_t expected_distinct, km_counter_t** out);
+/* bases and breaks as described above; k-mers never span two calls.  n == 0 is KM_OK without a launch. */
+int km_counter_add_bases(km_counter_t* c, const uint8_t* bytes, uint64_t n);
+/* FASTA (multi-line records) or 4-line FASTQ text, chosen by the first byte ('>' or '@'); "\r\n" is accepted.
+ * Whole lines are taken: a call may end in mid-line, *consumed says how much was taken, and the caller passes
+ * the rest again in front of the next block; final != 0 on the last call of a stream (the last line then needs
+ * no newline, and the next call may start a stream of the other format).  KM_E_FORMAT for a first byte that is
+ * neither, a FASTQ record that does not start with '@' or lacks its '+' line; km_last_error names the byte
+ * offset within the stream. */
+int km_counter_add_text(km_counter_t* c, const char* text, uint64_t n, int final, uint64_t* consumed);
+/* waits for everything added so far */
+int km_counter_stats(km_counter_t* c, km_counter_stats_t* s);
+/* compacts (count >= lower_count), builds the lookup table on the counter's device through the same path
+ * as kmjf_upload_from_device, frees the counting table; *out is an ordinary kmjf_t (kmjf_info, batches,
+ * queries, kmjf_close).  The counter may only be destroyed afterwards (and asked for its stats and records):
+ * KM_E_STATE for add_* after finish or a second finish. */
+int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t** out);
+/* after finish: copy the compacted records to the host (for writing a file), in no particular order;
+ * keys / counts may be NULL to ask for *n only; KM_E_CAPACITY if cap < n */
+int km_counter_records(km_counter_t* c, uint64_t* keys, uint32_t* counts, uint64_t cap, uint64_t* n);
+int km_counter_destroy(km_counter_t* c);
+/* The text stripper of km_counter_add_text alone, host only (no device is touched): writes the byte stream the
+ * counter would stage — sequence bytes, one '\n' where a read ends — to out[cap]; n bytes of text give at most
+ * n + 1 (KM_E_CAPACITY if cap is smaller, before anything is written). */
+int km_text_strip(km_text_state_t* st, const char* text, uint64_t n, int final, uint8_t* out, uint64_t cap,
+                  uint64_t* n_out, uint64_t* consumed);
+
 /* ---- measurement helpers (bench.py at N = 1 holds no device buffers of its own) ------------- */
 int km_device_sync(int device);                                    /* hipDeviceSynchronize on `device`          */
 /* device-to-device copy of `bytes` bytes, `reps` times: read + write GB/s (the box's large-copy

@@ -1,4 +1,4 @@
-"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line.
+"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, and ``count``.
 
 Same flags, same ``#key:value`` echo, same TSV and ``#Elapsed time`` trailer as
 km/tools/find_mutation.py:17-60 and km/argparser/find_mutation.py:4-58, so the
@@ -289,6 +289,27 @@ def main_min_cov(args, out=None):
         out.write("%s\t%d\t%d\t%d\t%d\t%.2f\t%d\t%d\n" % ((db,) + tuple(res)))
 
 
+def main_count(args, err=None):
+    """`jellyfish count -m K [-C] -L N -s SIZE -o OUT reads..` on the GPU (km_amd.count): the k-mers of the read
+    files counted on the device, the records with count >= -L written to OUT (read by every tool here; real
+    Jellyfish could not query the file, see km_amd.count.write_records)."""
+    err = sys.stderr if err is None else err
+    from . import count as kc
+    db, stats, counter = kc.count_files(args.reads, k=args.mer_len, canonical=args.canonical,
+                                        lower_count=args.lower_count, device=default_device(),
+                                        expected_distinct=args.size, keep_counter=True)
+    try:
+        keys, counts = counter.records()
+    finally:
+        counter.close()
+        db.close()
+    for key in ("bases", "kmers", "distinct", "slots", "n_grow"):
+        err.write("#%s:%d\n" % (key, stats[key]))
+    cmdline = ["km_amd", "count", "-m", str(args.mer_len)] + (["-C"] if args.canonical else []) + [
+        "-L", str(args.lower_count), "-s", str(args.size), "-o", args.output] + list(args.reads)
+    kc.write_records(args.output, keys, counts, args.mer_len, args.canonical, cmdline=cmdline)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(prog="km")
     sub = parser.add_subparsers(dest="_cmd")
@@ -309,6 +330,13 @@ def main(argv=None):
     lk.add_argument("-s", "--start", help="starting length (default: -s 10)", action="store", nargs="?",
                     default=10, type=int)
     lk.add_argument("target_fn", help="Filename of the reference sequence file or directory.", nargs="*")
+    ct = sub.add_parser("count", help="count the k-mers of FASTA / FASTQ reads on the GPU -> a .jf the other tools read")
+    ct.add_argument("-m", "--mer-len", type=int, default=31, help="length of mer (default: -m 31)")
+    ct.add_argument("-C", "--canonical", action="store_true", help="count both strands, canonical representation")
+    ct.add_argument("-L", "--lower-count", type=int, default=1, help="don't output k-mers with count < lower-count")
+    ct.add_argument("-s", "--size", type=int, default=0, help="expected number of distinct k-mers (0: grow as needed)")
+    ct.add_argument("-o", "--output", default="mer_counts.jf", help="output file (default: mer_counts.jf)")
+    ct.add_argument("reads", nargs="+", help="FASTA or FASTQ files, plain or gzip; - is stdin")
     args = parser.parse_args(argv)
     cmd = args._cmd
     del args._cmd
@@ -326,6 +354,8 @@ def main(argv=None):
         main_min_cov(args)
     elif cmd == "linear_kmin":
         main_linear_kmin(args)
+    elif cmd == "count":
+        main_count(args)
     else:
         parser.print_help(sys.stderr)
         sys.exit(1)

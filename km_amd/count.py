@@ -1,0 +1,109 @@
+"""Counting k-mers from read files on the GPU: what `jellyfish count -m k -C -L n -s size reads.fq` does in
+front of every km tool (``python -m km_amd count``).
+
+``count_files`` streams FASTA / FASTQ files (plain or gzip) through :class:`km_amd.lib.Counter` and returns the
+database built on the device from the counted records; ``write_records`` writes such records in the file
+framing the readers of this project load.  Only the standard library and numpy.
+"""
+
+import gzip
+import json
+import sys
+
+import numpy as np
+
+from . import lib as _lib
+
+BLOCK = 8 << 20          # text bytes read per add_text call
+
+
+def _open(path):
+    if path == "-":
+        return sys.stdin.buffer, False
+    fh = open(path, "rb")
+    magic = fh.read(2)
+    fh.seek(0)
+    if magic == b"\x1f\x8b":
+        return gzip.open(fh, "rb"), True
+    return fh, True
+
+
+def feed_file(counter, path, block=BLOCK):
+    """One file through counter.add_text in blocks, the unconsumed tail carried in front of the next block."""
+    fh, close = _open(path)
+    try:
+        tail = b""
+        while True:
+            data = fh.read(block)
+            if not data:
+                break
+            buf = tail + data if tail else data
+            used = counter.add_text(buf, final=False)
+            tail = buf[used:]
+        counter.add_text(tail, final=True)
+    finally:
+        if close:
+            fh.close()
+
+
+def count_files(paths, k=31, canonical=True, lower_count=1, device=0, expected_distinct=0, keep_counter=False):
+    """Count the k-mers of every read of `paths` (FASTA or 4-line FASTQ, gzip recognised by its magic, '-' =
+    stdin) -> (Database, stats).  stats is the dict of Counter.stats() before the cut at lower_count.
+    keep_counter=True returns (Database, stats, Counter) so that the caller can fetch the records."""
+    if isinstance(paths, (str, bytes)):
+        paths = [paths]
+    counter = _lib.Counter(k=k, canonical=canonical, device=device, expected_distinct=expected_distinct)
+    try:
+        for p in paths:
+            feed_file(counter, p)
+        stats = counter.stats()
+        db = counter.finish(lower_count)
+    except BaseException:
+        counter.close()
+        raise
+    if keep_counter:
+        return db, stats, counter
+    counter.close()
+    return db, stats
+
+
+def write_records(path, keys, counts, k, canonical, cmdline=None):
+    """Write (keys, counts) as a `binary/sorted`-framed file that kmjf_open / kmjf_load and the test oracle's
+    reader load: 9 ASCII digits (the header length), a JSON header (format, key_len = 2k, counter_len = 4,
+    canonical, ...) padded to 8 bytes, then one little-endian record per k-mer: ceil(2k / 8) key bytes and 4
+    count bytes (12 bytes for k = 29..32).  Records are sorted by key, so the same records give the same bytes
+    whatever order they arrive in.
+
+    Real Jellyfish orders the records of such a file by its matrix hash and binary-searches that order; it
+    could not query this file.  Readers that load all records (every reader here) do not care."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if keys.shape != counts.shape or keys.ndim != 1:
+        raise ValueError("keys and counts must be 1-d arrays of one length")
+    if not 2 <= int(k) <= 32:
+        raise ValueError("k=%d unsupported" % k)
+    order = np.argsort(keys, kind="stable")
+    keys, counts = keys[order], counts[order]
+    size = 16
+    while size < 2 * keys.size:
+        size <<= 1
+    header = {
+        "alignment": 8,
+        "canonical": bool(canonical),
+        "cmdline": list(cmdline) if cmdline is not None else ["km_amd", "count"],
+        "counter_len": 4,
+        "format": "binary/sorted",
+        "key_len": 2 * int(k),
+        "size": size,
+        "val_len": 32,
+    }
+    text = json.dumps(header, separators=(",", ":"), sort_keys=True).encode("ascii")
+    text += b"\0" * ((-(9 + len(text))) % 8)
+    kb = (2 * int(k) + 7) // 8
+    rec = np.zeros((keys.size, kb + 4), dtype=np.uint8)
+    rec[:, :kb] = keys.astype("<u8").view(np.uint8).reshape(-1, 8)[:, :kb]
+    rec[:, kb:] = counts.astype("<u4").view(np.uint8).reshape(-1, 4)
+    with open(path, "wb") as fh:
+        fh.write(b"%09d" % len(text))
+        fh.write(text)
+        fh.write(rec.tobytes())

@@ -1,0 +1,154 @@
+// count_kernel.h — counting k-mers from reads: a counting hash table in HBM and the three kernels that fill it,
+// grow it and empty it into the record arrays kmjf_upload_from_device takes.
+//
+// Table: open addressing with linear probing over 16-byte slots {u64 key, u32 count, u32 unused}; the key and
+// its count share one 16-byte piece of a line, so the add that follows a key's lookup hits the line that lookup
+// brought in.  Empty key = ~0 (device_common.h: EMPTY).  That value is also the k-mer T^32 of a non-canonical
+// k = 32 table (in canonical mode T^32 is stored as A^32 = 0): it is counted in a cell of its own (CM_ALLT).
+// Counts are integers added with atomics: the final set of (key, count) does not depend on arrival order.
+#pragma once
+#include "device_common.h"
+
+namespace kmd {
+
+struct __attribute__((aligned(16))) CountSlot {
+  uint64_t key;
+  uint32_t count;
+  uint32_t unused;
+};
+static_assert(sizeof(CountSlot) == 16, "one dwordx4 per slot");
+
+constexpr uint32_t COUNT_RUN = 32;      // window start positions a lane owns
+constexpr uint32_t COUNT_PAD = 128;     // readable bytes behind a staged chunk (the last lane loads 64 from its start)
+// cells of the counter's device meta block (u64 each)
+enum { CM_DISTINCT = 0, CM_BASES = 1, CM_KMERS = 2, CM_ALLT = 3, CM_ERROR = 4, CM_OUT = 5, CM_WORDS = 8 };
+
+__global__ void k_count_init(CountSlot* slots, uint64_t n_slots) {
+  uint4* p = reinterpret_cast<uint4*>(slots);
+  const uint4 empty = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots;
+       i += (uint64_t)gridDim.x * blockDim.x)
+    p[i] = empty;
+}
+
+// Find or claim the slot of `key` and add `add` to its count; returns 1 if the slot was claimed here.
+// The slot is read first; the compare-and-swap is issued only for a slot that looks empty, the add only once
+// the slot is known to hold the key.  A key, once written, never changes, so a slot read as another key is
+// another key for good.  The host keeps occupied <= slots / 2 (km_counter: the limit is checked against the
+// worst case of a chunk before the chunk is inserted), so an empty slot always ends the probe; the bound on
+// the loop only makes a broken invariant an error (CM_ERROR) instead of a hang.
+__device__ inline uint32_t count_add(CountSlot* tab, uint64_t smask, uint64_t key, uint32_t add,
+                                     unsigned long long* meta) {
+  uint64_t idx = mix64(key) & smask;
+  for (uint64_t step = 0; step <= smask; ++step) {
+    unsigned long long* kp = reinterpret_cast<unsigned long long*>(&tab[idx].key);
+    unsigned long long cur = __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t claimed = 0;
+    if (cur == EMPTY) {
+      cur = atomicCAS(kp, (unsigned long long)EMPTY, (unsigned long long)key);
+      if (cur == EMPTY) { cur = key; claimed = 1; }
+    }
+    if (cur == key) {
+      atomicAdd(&tab[idx].count, add);
+      return claimed;
+    }
+    idx = (idx + 1) & smask;
+  }
+  atomicAdd(&meta[CM_ERROR], 1ull);
+  return 0;
+}
+
+// One add per wave of the lanes' sum (nothing when the sum is 0).
+__device__ inline void wave_add(unsigned long long* cell, uint32_t v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if (lane_id() == 0 && v) atomicAdd(cell, (unsigned long long)v);
+}
+
+// text[0 .. n): bases (ACGTacgt) and breaks (any other byte).  Lane g owns the window starts
+// [32 g, 32 g + 32): it loads the 64 bytes from 32 g as four aligned dwordx4 (its own 32 and k - 1 <= 31 of its
+// neighbour's), rolls the forward and the reverse-complement key over them with a count of the bases since
+// the last break, and inserts every window of k bases that starts in its own range and ends before n.
+// own_from: bytes [0, own_from) were counted as bases by the piece before (pieces of one call overlap by k - 1).
+__global__ __launch_bounds__(256) void k_count_insert(const uint8_t* text, uint64_t n, uint32_t own_from, int k,
+                                                      int canonical, CountSlot* tab, uint64_t smask,
+                                                      unsigned long long* meta) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t s = g * COUNT_RUN;
+  uint32_t claimed = 0, bases = 0, kmers = 0, allt = 0;
+  if (s < n) {
+    const uint4* p = reinterpret_cast<const uint4*>(text + s);
+    const uint4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+    const uint32_t w[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w,
+                            q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
+    const uint64_t kmask = k >= 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+    const uint32_t rshift = 2u * (uint32_t)(k - 1);
+    const uint32_t jend = (uint32_t)k + COUNT_RUN - 1;        // bytes this lane looks at (<= 63)
+    uint64_t fwd = 0, rev = 0;
+    uint32_t run = 0;
+#pragma unroll
+    for (uint32_t d = 0; d < 16; ++d) {
+      if (4 * d < jend) {
+        const uint32_t word = w[d];
+#pragma unroll 1
+        for (uint32_t b = 0; b < 4; ++b) {
+          const uint32_t j = 4 * d + b;
+          const uint32_t ch = (word >> (8 * b)) & 0xFFu;
+          const uint32_t up = ch & 0xDFu;
+          const bool base = (up == 'A' || up == 'C' || up == 'G' || up == 'T') && s + j < n && j < jend;
+          uint32_t c = (ch >> 1) & 3u;                         // A 0, C 1, T 2, G 3
+          c ^= c >> 1;                                         // A 0, C 1, G 2, T 3
+          fwd = ((fwd << 2) | c) & kmask;
+          rev = (rev >> 2) | ((uint64_t)(3u - c) << rshift);
+          run = base ? run + 1 : 0;
+          bases += (base && j < COUNT_RUN && s + j >= own_from) ? 1u : 0u;
+          if (run >= (uint32_t)k) {                            // (j < jend: the window starts at j - k + 1 < 32)
+            const uint64_t key = (canonical && rev < fwd) ? rev : fwd;
+            ++kmers;
+            if (key == EMPTY) ++allt;
+            else claimed += count_add(tab, smask, key, 1u, meta);
+          }
+        }
+      }
+    }
+  }
+  wave_add(&meta[CM_DISTINCT], claimed);
+  wave_add(&meta[CM_BASES], bases);
+  wave_add(&meta[CM_KMERS], kmers);
+  wave_add(&meta[CM_ALLT], allt);
+}
+
+// Every occupied slot of the old table into the new one (twice the capacity or more), its count added.
+__global__ void k_count_rehash(const CountSlot* old_tab, uint64_t old_slots, CountSlot* tab, uint64_t smask,
+                               unsigned long long* meta) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_slots;
+       i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint4 v = *reinterpret_cast<const uint4*>(old_tab + i);
+    const uint64_t key = ((uint64_t)v.y << 32) | v.x;
+    if (key != EMPTY) (void)count_add(tab, smask, key, v.z, meta);
+  }
+}
+
+// The occupied slots with count >= lower_count, dense, in keys[] / counts[]: a ballot per wave, one atomic
+// append per wave.  n_slots is a multiple of 64 and so is the stride: a wave's lanes stay together.
+__global__ void k_count_compact(const CountSlot* tab, uint64_t n_slots, uint32_t lower_count, uint64_t* keys,
+                                uint32_t* counts, unsigned long long* meta) {
+  const uint32_t lane = (uint32_t)lane_id();
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots;
+       i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint4 v = *reinterpret_cast<const uint4*>(tab + i);
+    const uint64_t key = ((uint64_t)v.y << 32) | v.x;
+    const bool keep = key != EMPTY && v.z >= lower_count;
+    const unsigned long long m = __ballot(keep);
+    if (m == 0) continue;
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(&meta[CM_OUT], (unsigned long long)__popcll(m));
+    base = lane_u64(base, 0);
+    if (keep) {
+      const uint64_t at = base + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+      keys[at] = key;
+      counts[at] = v.z;
+    }
+  }
+}
+
+}  // namespace kmd

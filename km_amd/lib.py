@@ -34,6 +34,8 @@ SYMBOLS = [
     "km_batch_sizes", "km_batch_fetch", "km_batch_result", "km_batch_timings", "km_batch_graph_log", "km_batch_pump", "km_batch_debug_stamps", "km_batch_debug_counts",
     "km_device_sync", "km_device_copy_GBs", "km_probe_bench",
     "km_report_rows", "km_report_free", "km_linear_kmin", "km_strerror", "km_last_error",
+    "km_counter_create", "km_counter_add_bases", "km_counter_add_text", "km_counter_stats", "km_counter_finish",
+    "km_counter_records", "km_counter_destroy", "km_text_strip",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
 ]
 
@@ -63,6 +65,18 @@ class BatchSizes(C.Structure):
                 ("n_count_escapes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class CounterStats(C.Structure):
+    """km_counter_stats_t (include/kmgpu.h)."""
+    _fields_ = [("bases", C.c_uint64), ("kmers", C.c_uint64), ("distinct", C.c_uint64), ("slots", C.c_uint64),
+                ("n_grow", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TextState(C.Structure):
+    """km_text_state_t (include/kmgpu.h)."""
+    _fields_ = [("format", C.c_int32), ("line", C.c_int32), ("open", C.c_int32), ("reserved", C.c_int32),
+                ("offset", C.c_uint64)]
+
+
 _P16 = C.POINTER(C.c_uint16)
 _P32 = C.POINTER(C.c_uint32)
 _P64 = C.POINTER(C.c_uint64)
@@ -90,11 +104,17 @@ _lib = None
 # (they reference their database), then databases.  Without this a handle that is still alive when
 # Python tears its modules down is destroyed by __del__ in arbitrary order, possibly after the HIP
 # runtime has unloaded its state (round 2: a SIGSEGV inside __cxa_finalize under rocprofv3).
+_LIVE_COUNTERS = weakref.WeakSet()
 _LIVE_BATCHES = weakref.WeakSet()
 _LIVE_DATABASES = weakref.WeakSet()
 
 
 def close_all_handles():
+    for c in list(_LIVE_COUNTERS):
+        try:
+            c.close()
+        except Exception:
+            pass
     for b in list(_LIVE_BATCHES):
         try:
             b.close()
@@ -198,6 +218,14 @@ def load():
         "km_report_rows": [C.POINTER(ReportIn), C.POINTER(vp), C.POINTER(C.POINTER(C.c_uint64)),
                            C.POINTER(C.POINTER(C.c_int32))],
         "km_linear_kmin": [i32, vp, vp, u32, i32, vp, vp, vp, vp],
+        "km_counter_create": [i32, i32, i32, u64, C.POINTER(vp)],
+        "km_counter_add_bases": [vp, vp, u64],
+        "km_counter_add_text": [vp, vp, u64, i32, C.POINTER(u64)],
+        "km_counter_stats": [vp, C.POINTER(CounterStats)],
+        "km_counter_finish": [vp, u32, C.POINTER(vp)],
+        "km_counter_records": [vp, vp, vp, u64, C.POINTER(u64)],
+        "km_counter_destroy": [vp],
+        "km_text_strip": [C.POINTER(TextState), vp, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(u64)],
         "km_device_count": [C.POINTER(i32)],
         "km_device_sync": [i32],
         "km_device_copy_GBs": [i32, u64, i32, C.POINTER(dbl)],
@@ -392,6 +420,87 @@ class Database:
                                             int(n_cutoff), int(bool(forward)), ptr(mask),
                                             ptr(counts4)))
         return mask, counts4
+
+
+def _byte_view(data):
+    """A C-contiguous uint8 view of a bytes-like object (no copy for bytes, bytearray, memoryview, numpy)."""
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    return np.frombuffer(data, dtype=np.uint8)
+
+
+def strip_text(text, final=True, state=None):
+    """km_text_strip: the FASTA / FASTQ stripper of Counter.add_text alone, on the host (no GPU).
+    -> (stream bytes, consumed, state); pass `state` back in with the next block of the same stream."""
+    st = TextState() if state is None else state
+    buf = _byte_view(text)
+    out = np.empty(buf.size + 1, np.uint8)
+    n_out, consumed = C.c_uint64(), C.c_uint64()
+    check(load().km_text_strip(C.byref(st), ptr(buf) if buf.size else None, buf.size, int(bool(final)), ptr(out),
+                               out.size, C.byref(n_out), C.byref(consumed)))
+    return out[:n_out.value].tobytes(), int(consumed.value), st
+
+
+class Counter:
+    """k-mers counted from reads on the GPU (km_counter_*, include/kmgpu.h): what `jellyfish count -m k [-C]
+    -s expected_distinct` does.  add_bases / add_text feed it, finish() hands back a Database whose table was
+    built on the device from the counted records."""
+
+    def __init__(self, k=31, canonical=True, device=0, expected_distinct=0):
+        self._lib = load()
+        self._c = C.c_void_p()
+        self.k, self.canonical, self.device = int(k), bool(canonical), int(device)
+        check(self._lib.km_counter_create(self.device, self.k, int(self.canonical), int(expected_distinct),
+                                          C.byref(self._c)))
+        _LIVE_COUNTERS.add(self)
+
+    def close(self):
+        if self._c is not None and self._c.value:
+            self._lib.km_counter_destroy(self._c)
+        self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_bases(self, data):
+        """Bases (ACGTacgt) and breaks (any other byte); k-mers never span two calls."""
+        buf = _byte_view(data)
+        check(self._lib.km_counter_add_bases(self._c, ptr(buf) if buf.size else None, buf.size))
+
+    def add_text(self, data, final=False):
+        """FASTA or 4-line FASTQ text; returns how many bytes were taken (whole lines): pass the rest again in
+        front of the next block."""
+        buf = _byte_view(data)
+        consumed = C.c_uint64()
+        check(self._lib.km_counter_add_text(self._c, ptr(buf) if buf.size else None, buf.size, int(bool(final)),
+                                            C.byref(consumed)))
+        return int(consumed.value)
+
+    def stats(self):
+        """dict of km_counter_stats_t (waits for everything added so far)."""
+        s = CounterStats()
+        check(self._lib.km_counter_stats(self._c, C.byref(s)))
+        return {"bases": int(s.bases), "kmers": int(s.kmers), "distinct": int(s.distinct), "slots": int(s.slots),
+                "n_grow": int(s.n_grow)}
+
+    def finish(self, lower_count=1):
+        """Keep the k-mers with count >= lower_count and build the lookup table from them -> Database."""
+        h = C.c_void_p()
+        check(self._lib.km_counter_finish(self._c, int(lower_count), C.byref(h)))
+        return Database(h)
+
+    def records(self):
+        """(keys, counts) of the finished counter, as compacted on the device: in no particular order."""
+        n = C.c_uint64()
+        check(self._lib.km_counter_records(self._c, None, None, 0, C.byref(n)))
+        keys = np.zeros(n.value, np.uint64)
+        counts = np.zeros(n.value, np.uint32)
+        if n.value:
+            check(self._lib.km_counter_records(self._c, ptr(keys), ptr(counts), n.value, C.byref(n)))
+        return keys, counts
 
 
 class Batch:

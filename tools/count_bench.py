@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""km_counter (counting k-mers from reads on the GPU) at two table sizes; prints one JSON line.
+
+Input: seeded synthetic reads, 100 nt, drawn from both strands of a seeded random genome, 1 % substitutions and
+0.1 % N.  Two sizes: `cache` (a 100 kb genome at 200x through 1 MiB staging buffers: the counting table stays at
+134 MB, inside the 256 MB last-level cache) and `hbm` (a 100 Mb genome at 2x: a table of some GB).  Per size,
+timed as wall time around calls that end in km_counter_stats (which waits for the device):
+  add_bases  - pre-stripped bytes, table sized in advance (expected_distinct): k-mers/s, and the table traffic
+               that stands for (8-byte key read + 4-byte add per k-mer, 8-byte compare-and-swap per new key)
+  add_text   - the same reads as FASTQ text in 8 MB blocks, table grown from the default: bytes/s, n_grow
+  finish     - compaction + lookup-table build, seconds
+and km_device_copy_GBs of the same run for scale.
+
+usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from km_amd import lib as kmlib  # noqa: E402
+
+ACGT = np.frombuffer(b"ACGT", np.uint8)
+COMP = np.zeros(256, np.uint8)
+COMP[list(b"ACGT")] = list(b"TGCA")
+SIZES = {"cache": (100_000, 200_000, 1 << 20), "hbm": (100_000_000, 2_000_000, None)}   # genome, reads, staging
+
+
+def make_reads(rng, genome_len, n_reads, read_len=100):
+    """(n_reads, read_len) uint8."""
+    genome = ACGT[rng.integers(0, 4, genome_len)]
+    out = np.empty((n_reads, read_len), np.uint8)
+    for lo in range(0, n_reads, 200_000):
+        hi = min(n_reads, lo + 200_000)
+        starts = rng.integers(0, genome_len - read_len + 1, hi - lo)
+        part = genome[starts[:, None] + np.arange(read_len)[None, :]]
+        rev = rng.integers(0, 2, hi - lo).astype(bool)
+        part[rev] = COMP[part[rev]][:, ::-1]
+        sub = rng.random(part.shape) < 0.01
+        part[sub] = ACGT[rng.integers(0, 4, int(sub.sum()))]
+        part[rng.random(part.shape) < 0.001] = ord("N")
+        out[lo:hi] = part
+    return out
+
+
+def as_stream(reads):
+    rows = np.full((reads.shape[0], reads.shape[1] + 1), ord("\n"), np.uint8)
+    rows[:, :-1] = reads
+    return rows.reshape(-1)
+
+
+def as_fastq(reads):
+    n, ln = reads.shape
+    rows = np.empty((n, 3 + ln + 3 + ln + 1), np.uint8)
+    rows[:, :3] = np.frombuffer(b"@r\n", np.uint8)
+    rows[:, 3:3 + ln] = reads
+    rows[:, 3 + ln:6 + ln] = np.frombuffer(b"\n+\n", np.uint8)
+    rows[:, 6 + ln:6 + 2 * ln] = ord("I")
+    rows[:, -1] = ord("\n")
+    return rows.reshape(-1)
+
+
+def run_size(name, k, device, rng):
+    genome_len, n_reads, stage = SIZES[name]
+    if stage:
+        os.environ["KM_COUNT_STAGE_BYTES"] = str(stage)
+    else:
+        os.environ.pop("KM_COUNT_STAGE_BYTES", None)
+    reads = make_reads(rng, genome_len, n_reads)
+    stream, text = as_stream(reads), as_fastq(reads)
+    warm = kmlib.Counter(k=k, device=device)              # code object load, first allocations
+    warm.add_bases(stream[:1_000_000])
+    warm.finish().close()
+    warm.close()
+
+    sized = kmlib.Counter(k=k, device=device, expected_distinct=0 if stage else 2 * genome_len + stream.size // 20)
+    t0 = time.perf_counter()
+    sized.add_bases(stream)
+    st = sized.stats()
+    t_bases = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    db = sized.finish(2)
+    t_finish = time.perf_counter() - t0
+    n_kept = int(db.info.n_records)
+    db.close()
+    sized.close()
+
+    grown = kmlib.Counter(k=k, device=device)
+    block = 8 << 20
+    t0 = time.perf_counter()
+    pos, tail = 0, b""
+    while pos < text.size:
+        buf = text[pos:pos + block]
+        pos += block
+        if len(tail):
+            buf = np.concatenate([tail, buf])
+        used = grown.add_text(buf, final=False)
+        tail = buf[used:]
+    grown.add_text(tail, final=True)
+    st_text = grown.stats()
+    t_text = time.perf_counter() - t0
+    assert (st_text["kmers"], st_text["distinct"]) == (st["kmers"], st["distinct"])
+    grown.finish(2).close()
+    grown.close()
+    traffic = 12 * st["kmers"] + 8 * st["distinct"]
+    return {
+        "reads": n_reads, "bases": st["bases"], "kmers": st["kmers"], "distinct": st["distinct"],
+        "kept_at_L2": n_kept, "table_slots": st["slots"], "table_MB": st["slots"] * 16 / 1e6,
+        "staging_bytes": stage or 16 << 20,
+        "add_bases_s": t_bases, "add_bases_kmers_per_s": st["kmers"] / t_bases, "add_bases_n_grow": st["n_grow"],
+        "add_bases_table_GBs": traffic / t_bases / 1e9,
+        "add_text_s": t_text, "add_text_bytes_per_s": text.size / t_text, "add_text_kmers_per_s": st["kmers"] / t_text,
+        "add_text_n_grow": st_text["n_grow"], "add_text_table_slots": st_text["slots"],
+        "finish_s": t_finish,
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--sizes", default="cache,hbm")
+    ap.add_argument("-k", type=int, default=31)
+    args = ap.parse_args()
+    kmlib.load()
+    rng = np.random.default_rng(2026)
+    out = {"tool": "count_bench", "k": args.k, "sizes": {}}
+    for name in args.sizes.split(","):
+        out["sizes"][name] = run_size(name, args.k, args.device, rng)
+    out["km_device_copy_GBs"] = kmlib.device_copy_GBs(args.device, 1 << 30, 10)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

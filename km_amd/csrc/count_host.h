@@ -1,0 +1,288 @@
+// count_host.h — km_counter_*, km_text_strip (host part of kmgpu.hip; device side: count_kernel.h, fastx_strip.h)
+// ------------------------------------------------------------------ counting k-mers from reads
+// km_counter (include/kmgpu.h): text or bases are staged in two pinned buffers that take turns,
+// copied and inserted (count_kernel.h) on the counter's own stream, so the host strips the next block while the
+// device inserts the last.  What is staged is ONE byte stream (bases and breaks); it is cut into pieces of the
+// staging size that overlap by exactly k - 1 bytes, and a piece counts the windows that lie wholly inside it:
+// piece i covers [i (S - k + 1), i (S - k + 1) + S), so a window of k bytes lies wholly inside exactly one piece.
+namespace {
+constexpr uint64_t COUNT_STAGE_BYTES = 16ull << 20;     // per pinned buffer (KM_COUNT_STAGE_BYTES: tests)
+constexpr uint64_t COUNT_DEFAULT_SLOTS = 1ull << 16;
+uint64_t key_space(int k) { return k >= 32 ? ~0ull : (1ull << (2 * k)); }
+}  // namespace
+
+struct km_counter {
+  int device = 0, k = 0, canonical = 0;
+  Stream st;                              // (declared first: destroyed last)
+  DevBuf<CountSlot> table;
+  uint64_t slots = 0;
+  DevBuf<unsigned long long> meta;        // CM_* cells
+  DevBuf<uint8_t> d_text;                 // the staged piece on the device (one: copy and kernel are stream-ordered)
+  Pinned pin[2];
+  Event copied[2];                        // the copy out of pin[i] is done: the host may write it again
+  uint64_t stage = COUNT_STAGE_BYTES;
+  int cur = 0;
+  uint64_t fill = 0;                      // bytes in pin[cur]
+  uint32_t own_from = 0;                  // of those, carried over from the piece before
+  uint64_t occ_ub = 0;                    // upper bound of the occupied slots once everything enqueued has run
+  uint32_t n_grow = 0;
+  bool finished = false;
+  km_text_state_t text = {0, 0, 0, 0, 0};
+  km_counter_stats_t last = {0, 0, 0, 0, 0, 0};
+  DevBuf<uint64_t> out_keys;
+  DevBuf<uint32_t> out_counts;
+  uint64_t n_out = 0;
+  ~km_counter() {
+    (void)hipSetDevice(device);
+    if (st) (void)hipStreamSynchronize(st);
+  }
+};
+
+// waits for everything enqueued
+static int counter_read_meta(km_counter* c, unsigned long long* m) {
+  HIPCHK(hipMemcpyAsync(m, c->meta, CM_WORDS * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  if (m[CM_ERROR]) return fail(KM_E_HIP, "counting table ran full (%llu keys not placed)", m[CM_ERROR]);
+  c->last.bases = m[CM_BASES];
+  c->last.kmers = m[CM_KMERS];
+  c->last.distinct = m[CM_DISTINCT] + (m[CM_ALLT] ? 1 : 0);
+  c->last.slots = c->slots;
+  c->last.n_grow = c->n_grow;
+  return KM_OK;
+}
+
+// Room for `windows` more keys, every one of them new: the load limit (1/2) is checked against that worst case
+// BEFORE the piece is inserted, so an insert kernel never meets a full table.  The bound kept on the host only
+// grows; when it no longer fits, the exact occupancy is read (one wait for the pieces in flight) and, if that
+// does not fit either, the table is rehashed into one of 2^d times the capacity.
+static int counter_reserve(km_counter* c, uint64_t windows) {
+  const uint64_t space = key_space(c->k);
+  auto need_of = [&](uint64_t occ) { return std::min(occ + windows, space); };
+  if (need_of(c->occ_ub) <= c->slots / 2) { c->occ_ub = need_of(c->occ_ub); return KM_OK; }
+  unsigned long long m[CM_WORDS];
+  KMCHK(counter_read_meta(c, m));
+  const uint64_t need = need_of(m[CM_DISTINCT]);
+  uint64_t ns = c->slots;
+  uint32_t d = 0;
+  while (need > ns / 2) {
+    if (ns >> 62) return fail(KM_E_CAPACITY, "counting table would exceed 2^62 slots");
+    ns <<= 1;
+    ++d;
+  }
+  if (d) {
+    DevBuf<CountSlot> grown;
+    KMCHK(grown.alloc(ns));
+    hipLaunchKernelGGL(k_count_init, dim3(grid_for(ns, 256)), dim3(256), 0, c->st, grown.p, ns);
+    hipLaunchKernelGGL(k_count_rehash, dim3(grid_for(c->slots, 256)), dim3(256), 0, c->st, c->table.p, c->slots,
+                       grown.p, ns - 1, c->meta.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->table = std::move(grown);
+    c->slots = ns;
+    c->n_grow += d;
+  }
+  c->occ_ub = need;
+  return KM_OK;
+}
+
+// Enqueue the piece in pin[cur] (copy + insert) and turn to the other buffer, which starts with the last k - 1
+// bytes of this one.  Nothing to do while the buffer holds only such carried bytes.
+static int counter_flush(km_counter* c) {
+  if (c->fill <= c->own_from) return KM_OK;
+  const uint64_t n = c->fill;
+  KMCHK(counter_reserve(c, n >= (uint64_t)c->k ? n - c->k + 1 : 0));
+  HIPCHK(hipMemcpyAsync(c->d_text, c->pin[c->cur], n, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipEventRecord(c->copied[c->cur], c->st));
+  const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
+  hipLaunchKernelGGL(k_count_insert, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, c->st, c->d_text.p, n,
+                     c->own_from, c->k, c->canonical, c->table.p, c->slots - 1, c->meta.p);
+  HIPCHK(hipGetLastError());
+  const int nxt = c->cur ^ 1;
+  HIPCHK(hipEventSynchronize(c->copied[nxt]));
+  const uint64_t keep = std::min<uint64_t>((uint64_t)c->k - 1, n);
+  memcpy(c->pin[nxt], c->pin[c->cur] + n - keep, keep);
+  c->fill = keep;
+  c->own_from = (uint32_t)keep;
+  c->cur = nxt;
+  return KM_OK;
+}
+
+static int counter_append(km_counter* c, const uint8_t* p, uint64_t n) {
+  while (n) {
+    if (c->fill == c->stage) {
+      KMCHK(counter_flush(c));
+    }
+    const uint64_t take = std::min(n, c->stage - c->fill);
+    memcpy(c->pin[c->cur] + c->fill, p, take);
+    c->fill += take;
+    p += take;
+    n -= take;
+  }
+  return KM_OK;
+}
+
+extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expected_distinct, km_counter_t** out) {
+  if (!out) return fail(KM_E_ARG, "null argument");
+  if (k < 2 || k > 32) return fail(KM_E_K, "k=%d unsupported", k);
+  if (device < 0) return fail(KM_E_ARG, "device %d", device);
+  if (expected_distinct >> 60) return fail(KM_E_ARG, "expected_distinct too large");
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<km_counter> c(new (std::nothrow) km_counter);
+  if (!c) return fail(KM_E_NOMEM, "host allocation failed");
+  c->device = device;
+  c->k = k;
+  c->canonical = canonical ? 1 : 0;
+  if (const char* e = getenv("KM_COUNT_STAGE_BYTES")) c->stage = std::max<uint64_t>(256, strtoull(e, nullptr, 10));
+  c->slots = COUNT_DEFAULT_SLOTS;
+  if (expected_distinct) {
+    c->slots = 64;
+    while (c->slots / 2 < expected_distinct) c->slots <<= 1;
+  }
+  HIPCHK(hipStreamCreateWithFlags(&c->st.h, hipStreamNonBlocking));
+  int rc = c->table.alloc(c->slots);
+  if (rc == KM_OK) rc = c->meta.alloc(CM_WORDS);
+  if (rc == KM_OK) rc = c->d_text.alloc(c->stage + COUNT_PAD);
+  if (rc != KM_OK) return rc;
+  for (int i = 0; i < 2; ++i) {
+    hipError_t e = hipHostMalloc((void**)&c->pin[i].h, c->stage + COUNT_PAD, hipHostMallocDefault);
+    if (e != hipSuccess) { c->pin[i].h = nullptr; return fail(KM_E_NOMEM, "pinned staging buffer: %s", hipGetErrorString(e)); }
+    HIPCHK(hipEventCreateWithFlags(&c->copied[i].h, hipEventDisableTiming));
+  }
+  HIPCHK(hipMemsetAsync(c->meta, 0, CM_WORDS * 8, c->st));
+  hipLaunchKernelGGL(k_count_init, dim3(grid_for(c->slots, 256)), dim3(256), 0, c->st, c->table.p, c->slots);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->st));
+  c->last.slots = c->slots;
+  *out = c.release();
+  return KM_OK;
+}
+
+extern "C" int km_counter_add_bases(km_counter_t* c, const uint8_t* bytes, uint64_t n) {
+  if (!c || (n && !bytes)) return fail(KM_E_ARG, "null argument");
+  if (c->finished) return fail(KM_E_STATE, "counter already finished");
+  if (n == 0) return KM_OK;
+  HIPCHK(hipSetDevice(c->device));
+  int rc = counter_append(c, bytes, n);
+  const uint8_t brk = kmstrip::BREAK;                 // k-mers never span two calls
+  if (rc == KM_OK) rc = counter_append(c, &brk, 1);
+  return rc;
+}
+
+namespace {
+struct CounterSink {
+  km_counter* c;
+  int rc = KM_OK;
+  void bytes(const uint8_t* p, uint64_t n) { if (rc == KM_OK) rc = counter_append(c, p, n); }
+  void brk() { const uint8_t b = kmstrip::BREAK; bytes(&b, 1); }
+};
+struct BufferSink {
+  uint8_t* out;
+  uint64_t n = 0;
+  void bytes(const uint8_t* p, uint64_t len) { memcpy(out + n, p, len); n += len; }
+  void brk() { out[n++] = kmstrip::BREAK; }
+};
+int strip_failed(const kmstrip::Result& r) {
+  return fail(KM_E_FORMAT, "%s at byte offset %llu", kmstrip::error_text(r.error), (unsigned long long)r.error_offset);
+}
+}  // namespace
+
+extern "C" int km_counter_add_text(km_counter_t* c, const char* text, uint64_t n, int final, uint64_t* consumed) {
+  if (!c || !consumed || (n && !text)) return fail(KM_E_ARG, "null argument");
+  if (c->finished) return fail(KM_E_STATE, "counter already finished");
+  *consumed = 0;
+  if (n == 0 && !final) return KM_OK;
+  HIPCHK(hipSetDevice(c->device));
+  CounterSink sink{c};
+  const kmstrip::Result r = kmstrip::strip(&c->text, text, n, final, sink);
+  *consumed = r.consumed;
+  if (sink.rc != KM_OK) return sink.rc;
+  if (r.error) return strip_failed(r);
+  return KM_OK;
+}
+
+extern "C" int km_text_strip(km_text_state_t* st, const char* text, uint64_t n, int final, uint8_t* out, uint64_t cap,
+                             uint64_t* n_out, uint64_t* consumed) {
+  if (!st || !out || !n_out || !consumed || (n && !text)) return fail(KM_E_ARG, "null argument");
+  *n_out = *consumed = 0;
+  if (cap < n + 1) return fail(KM_E_CAPACITY, "output buffer too small (%llu bytes of text need %llu)",
+                               (unsigned long long)n, (unsigned long long)n + 1);
+  BufferSink sink{out};
+  const kmstrip::Result r = kmstrip::strip(st, text, n, final, sink);
+  *n_out = sink.n;
+  *consumed = r.consumed;
+  if (r.error) return strip_failed(r);
+  return KM_OK;
+}
+
+extern "C" int km_counter_stats(km_counter_t* c, km_counter_stats_t* s) {
+  if (!c || !s) return fail(KM_E_ARG, "null argument");
+  if (!c->finished) {
+    HIPCHK(hipSetDevice(c->device));
+    int rc = counter_flush(c);
+    unsigned long long m[CM_WORDS];
+    if (rc == KM_OK) rc = counter_read_meta(c, m);
+    if (rc != KM_OK) return rc;
+  }
+  *s = c->last;
+  return KM_OK;
+}
+
+extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t** out) {
+  if (!c || !out) return fail(KM_E_ARG, "null argument");
+  if (c->finished) return fail(KM_E_STATE, "counter already finished");
+  HIPCHK(hipSetDevice(c->device));
+  int rc = counter_flush(c);
+  unsigned long long m[CM_WORDS];
+  if (rc == KM_OK) rc = counter_read_meta(c, m);
+  if (rc != KM_OK) return rc;
+  const uint64_t cap = m[CM_DISTINCT] + 1;
+  rc = c->out_keys.alloc(cap);
+  if (rc == KM_OK) rc = c->out_counts.alloc(cap);
+  if (rc != KM_OK) return rc;
+  HIPCHK(hipMemsetAsync(c->meta.p + CM_OUT, 0, 8, c->st));
+  hipLaunchKernelGGL(k_count_compact, dim3(grid_for(c->slots, 256)), dim3(256), 0, c->st, c->table.p, c->slots,
+                     lower_count, c->out_keys.p, c->out_counts.p, c->meta.p);
+  HIPCHK(hipGetLastError());
+  KMCHK(counter_read_meta(c, m));
+  uint64_t n = m[CM_OUT];
+  if (n > m[CM_DISTINCT]) return fail(KM_E_HIP, "compaction wrote %llu records for %llu keys", m[CM_OUT], m[CM_DISTINCT]);
+  if (m[CM_ALLT] && m[CM_ALLT] >= lower_count) {        // T^32 of a non-canonical k = 32 table (count_kernel.h)
+    const uint64_t key = EMPTY;
+    const uint32_t cnt = (uint32_t)std::min<unsigned long long>(m[CM_ALLT], 0xFFFFFFFFull);
+    HIPCHK(hipMemcpyAsync(c->out_keys.p + n, &key, 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(c->out_counts.p + n, &cnt, 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    ++n;
+  }
+  kmjf_t* h = nullptr;
+  KMCHK(kmjf_create(c->k, c->canonical, &h));
+  rc = kmjf_upload_from_device(h, c->device, c->out_keys, c->out_counts, n, c->st);
+  if (rc != KM_OK) { kmjf_close(h); return rc; }
+  c->n_out = n;
+  c->table.release();
+  c->d_text.release();
+  c->finished = true;
+  *out = h;
+  return KM_OK;
+}
+
+extern "C" int km_counter_records(km_counter_t* c, uint64_t* keys, uint32_t* counts, uint64_t cap, uint64_t* n) {
+  if (!c || !n) return fail(KM_E_ARG, "null argument");
+  if (!c->finished) return fail(KM_E_STATE, "km_counter_finish comes first");
+  *n = c->n_out;
+  if (!keys && !counts) return KM_OK;
+  if (!keys || !counts) return fail(KM_E_ARG, "null argument");
+  if (cap < c->n_out) return fail(KM_E_CAPACITY, "%llu records, room for %llu", (unsigned long long)c->n_out,
+                                  (unsigned long long)cap);
+  if (c->n_out == 0) return KM_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpyAsync(keys, c->out_keys, c->n_out * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(counts, c->out_counts, c->n_out * 4, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return KM_OK;
+}
+
+extern "C" int km_counter_destroy(km_counter_t* c) {
+  delete c;
+  return KM_OK;
+}

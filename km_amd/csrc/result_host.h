@@ -1,0 +1,348 @@
+// result_host.h — what reads a delivered step: finish_result and the exports over it (km_batch_result, _pump, _sizes,
+// _fetch), the diagnostics exports and the measurement helpers (host part of kmgpu.hip; the step itself: batch_host.h)
+// Wait for an event; KM_SPIN_US=n polls it for the first n microseconds instead of putting the
+// thread to sleep at once (default 0: on the boxes measured a polling consumer gained nothing,
+// 0.315 against 0.312 ms per delivered step).
+static hipError_t wait_event_hot(hipEvent_t ev) {
+  const long spin_us = knobs().spin_us;
+  if (spin_us > 0) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+      const hipError_t e = hipEventQuery(ev);
+      if (e != hipErrorNotReady) return e;
+      if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > spin_us) break;
+    }
+  }
+  return hipEventSynchronize(ev);
+}
+
+// Results of the last run in the pinned delivery buffer (delivering now if the run did not).
+// `need_full`: a lean delivery (pending or ready) is replaced by a full one.
+static int finish_result(km_batch* b, bool need_full) {
+  if (!b->ran_walk) return fail(KM_E_STATE, "nothing has run yet");
+  const bool partial = b->out.lean || b->out.count16;       // the pending / ready delivery is not the full 32-bit form
+  if (b->out.result_ready && !(need_full && partial)) return KM_OK;
+  HIPCHK(hipSetDevice(b->device));
+  hipStream_t st = b->last_stream;
+  if (need_full && partial && (b->out.deliver_pending || b->out.result_ready)) {
+    HIPCHK(hipEventSynchronize(b->out.ev_out));
+    b->out.deliver_pending = b->out.result_ready = false;
+  }
+  if (!b->out.deliver_pending) {
+    KMCHK(km_batch_sync(b));
+    KMCHK(enqueue_deliver(b, st, false));
+  }
+  const OutLayout L = out_layout(b->n_targets);
+  const unsigned long long* T = reinterpret_cast<const unsigned long long*>(b->out.h_out + L.totals);
+  for (int attempt = 0;; ++attempt) {
+    HIPCHK(wait_event_hot(b->out.ev_out));
+    if (knobs().debug_deliver) {                      // timing ablation (diagnostics build only): nothing valid arrived
+      b->out.deliver_pending = false; b->out.result_ready = true;
+      return KM_OK;
+    }
+    if (T[OT_SERIAL] != b->out.serial) return fail(KM_E_HIP, "delivery buffer out of step");
+    const unsigned long long nh = T[OT_NEEDS_HOST];
+    if (b->hints.observe(T[OT_N_FLAGGED], b->ran_graph && b->graph_mode == 0 ? &T[OT_N_GRAPH_LIST] : nullptr)) b->drop_graph();
+    if ((nh & 1ull) || T[OT_N_BIG_DEV]) arm_big_device(b);
+    if (!nh && b->out.count16 && T[OT_N_ESC] > OUT_ESC_CAP) {
+      // more counts >= 65535 than the escape list holds: this batch is delivered with 32-bit counts
+      if (attempt >= 4) return fail(KM_E_NOMEM, "result delivery keeps failing");
+      KMCHK(enqueue_deliver(b, st, b->out.lean, false));
+      continue;
+    }
+    if (!nh) break;
+    if (attempt >= 4) return fail(KM_E_NOMEM, "result delivery keeps failing");
+    if (nh & 1ull) {
+      b->synced = false;
+      KMCHK(km_batch_sync(b));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    // (2: everything is final, only the tail is larger than the buffer)
+    KMCHK(ensure_out(b, nh == 2ull ? T[OT_TAIL_BYTES] + 4096 : default_tail_bytes(b, b->nodes.node_pool_used, b->nodes.node_pool_used)));
+    T = reinterpret_cast<const unsigned long long*>(b->out.h_out + L.totals);
+    KMCHK(enqueue_deliver(b, st, b->out.lean, b->out.count16));
+  }
+  const uint64_t tail = T[OT_TAIL_BYTES];
+  if (tail > b->out.copied_tail)
+    HIPCHK(hipMemcpy(b->out.h_out + L.a_bytes + b->out.copied_tail, b->out.d_out + L.a_bytes + b->out.copied_tail,
+                     tail - b->out.copied_tail, hipMemcpyDeviceToHost));
+  b->out.tail_guess = tail + tail / 16 + 4096;
+  if (b->out.count16 && T[OT_N_ESC] > 1) {
+    // the escape list in node order (the delivery kernel appends as its waves come)
+    const uint32_t ne = (uint32_t)T[OT_N_ESC];
+    uint64_t* en = reinterpret_cast<uint64_t*>(b->out.h_out + L.esc_node);
+    uint32_t* ev = reinterpret_cast<uint32_t*>(b->out.h_out + L.esc_value);
+    std::vector<std::pair<uint64_t, uint32_t>> tmp(ne);
+    for (uint32_t i = 0; i < ne; ++i) tmp[i] = {en[i], ev[i]};
+    std::sort(tmp.begin(), tmp.end());
+    for (uint32_t i = 0; i < ne; ++i) { en[i] = tmp[i].first; ev[i] = tmp[i].second; }
+  }
+  b->out.deliver_pending = false;
+  b->out.result_ready = true;
+  return KM_OK;
+}
+
+static void view_of_result(const km_batch* b, km_batch_out_t* v) {
+  const OutLayout L = out_layout(b->n_targets);
+  unsigned char* h = b->out.h_out;
+  const unsigned long long* T = reinterpret_cast<const unsigned long long*>(h + L.totals);
+  unsigned char* tail = h + L.a_bytes;
+  memset(v, 0, sizeof *v);
+  v->status = reinterpret_cast<uint32_t*>(h + L.status);
+  v->n_ref = reinterpret_cast<uint32_t*>(h + L.n_ref);
+  v->probes = reinterpret_cast<uint64_t*>(h + L.probes);
+  v->node_off = reinterpret_cast<uint64_t*>(h + L.node_off);
+  v->extra_off = reinterpret_cast<uint64_t*>(h + L.extra_off);
+  v->path_off = reinterpret_cast<uint32_t*>(h + L.path_off);
+  v->ref_max_cov = reinterpret_cast<uint32_t*>(h + L.ref_max);
+  if (b->out.count16) {
+    v->node_count16 = reinterpret_cast<uint16_t*>(tail + T[OT_OFF_COUNT]);
+    v->count_esc_node = reinterpret_cast<uint64_t*>(h + L.esc_node);
+    v->count_esc_value = reinterpret_cast<uint32_t*>(h + L.esc_value);
+  } else {
+    v->node_count = reinterpret_cast<uint32_t*>(tail + T[OT_OFF_COUNT]);
+  }
+  v->extra_kmer = reinterpret_cast<uint64_t*>(tail + T[OT_OFF_EXTRA]);
+  v->path_len = reinterpret_cast<uint32_t*>(tail + T[OT_OFF_PLEN]);
+  v->path_min_cov = reinterpret_cast<uint32_t*>(tail + T[OT_OFF_PMIN]);
+  v->run_off = reinterpret_cast<uint64_t*>(tail + T[OT_OFF_RUNOFF]);
+  v->run_start = reinterpret_cast<uint32_t*>(tail + T[OT_OFF_RSTART]);
+  v->run_len = reinterpret_cast<uint32_t*>(tail + T[OT_OFF_RLEN]);
+}
+
+static void sizes_of_result(const km_batch* b, km_batch_sizes_t* s) {
+  const unsigned long long* T = reinterpret_cast<const unsigned long long*>(b->out.h_out + out_layout(b->n_targets).totals);
+  memset(s, 0, sizeof *s);
+  s->n_targets = b->n_targets;
+  s->n_paths = (uint32_t)T[OT_N_PATHS];
+  s->n_nodes = T[OT_N_NODES];
+  s->n_runs = T[OT_N_RUNS];
+  s->n_extra = T[OT_N_EXTRA];
+  s->logical_probes = T[OT_PROBES];
+  s->table_fetches = T[OT_FETCHES];
+  s->n_big_tier = b->big.n_big + (b->big.bigdev_ran ? (uint32_t)T[OT_N_BIG_DEV] : 0u);
+  s->n_flagged = (uint32_t)T[OT_N_FLAGGED];
+  s->seed_probes = T[OT_SEED_PROBES];
+  s->n_count_escapes = b->out.count16 ? (uint32_t)T[OT_N_ESC] : 0;
+}
+
+extern "C" int km_batch_result(km_batch_t* b, km_batch_out_t* view, km_batch_sizes_t* sizes) {
+  if (!b) return fail(KM_E_ARG, "null argument");
+  KMCHK(finish_result(b, false));
+  if (view) view_of_result(b, view);
+  if (sizes) sizes_of_result(b, sizes);
+  return KM_OK;
+}
+
+// `steps` runs over `n` batches in flight, round robin: before a batch is run again its last
+// delivery is awaited (km_batch_result), at the end every batch's.  The loop a pipelined consumer
+// writes, kept on the library's side of the ABI so that an interpreter between two launches does
+// not sit in the timed region (diagnostics / bench; tools/launch_cost.py).
+extern "C" int km_batch_pump(km_batch_t* const* bs, void* const* streams, int n, int steps, int stages) {
+  if (!bs || n <= 0 || steps < 0) return fail(KM_E_ARG, "bad argument");
+  const bool deliver = (stages & KM_RUN_DELIVER) != 0;
+  for (int i = 0; i < steps; ++i) {
+    km_batch_t* b = bs[i % n];
+    if (i >= n && deliver) KMCHK(finish_result(b, false));
+    KMCHK(km_batch_run(b, stages, streams ? streams[i % n] : nullptr));
+  }
+  for (int q = 0; q < std::min(n, steps); ++q) {
+    KMCHK(deliver ? finish_result(bs[q], false) : km_batch_sync(bs[q]));
+  }
+  return KM_OK;
+}
+
+extern "C" int km_batch_debug_stamps(km_batch_t* b, uint64_t* dst, uint64_t cap_words, uint64_t* n_words) {
+  if (!b || !n_words) return fail(KM_E_ARG, "null argument");
+  KMCHK(km_batch_sync(b));
+  const uint64_t n = b->probes.d_stamps.p ? 16ull * (SEED_BLOCK / 64) * b->in.n_items : 0;
+  *n_words = n;
+  if (!dst || !n) return KM_OK;
+  if (cap_words < n) return fail(KM_E_CAPACITY, "stamp buffer too small");
+  HIPCHK(hipMemcpy(dst, b->probes.d_stamps.p, n * 8, hipMemcpyDeviceToHost));
+  return KM_OK;
+}
+
+// ---- measurement helpers for consumers that hold no device buffers of their own (bench.py at N = 1
+// runs without PyTorch in the process: the library is then served by the ROCm installation's HIP runtime,
+// as it is for a C consumer)
+extern "C" int km_device_sync(int device) {
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipDeviceSynchronize());
+  return KM_OK;
+}
+
+// Device-to-device copy of `bytes` bytes, `reps` times: read + write bandwidth in GB/s (the box's
+// large-copy rate beside the 8 TB/s spec).
+extern "C" int km_device_copy_GBs(int device, uint64_t bytes, int reps, double* gbs) {
+  if (!gbs || !bytes || reps < 1) return fail(KM_E_ARG, "bad argument");
+  HIPCHK(hipSetDevice(device));
+  DevBuf<unsigned char> a, b;
+  if (a.alloc(bytes) != KM_OK || b.alloc(bytes) != KM_OK) return fail(KM_E_NOMEM, "hipMalloc failed");
+  Event e0, e1;
+  hipError_t e = hipEventCreate(&e0.h);
+  if (e == hipSuccess) e = hipEventCreate(&e1.h);
+  if (e == hipSuccess) e = hipMemcpy(b, a, bytes, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
+  for (int i = 0; i < reps && e == hipSuccess; ++i) e = hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, nullptr);
+  if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
+  if (e == hipSuccess) e = hipEventSynchronize(e1);
+  float ms = 0;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+  if (e != hipSuccess) return fail(KM_E_HIP, "copy bandwidth measurement failed: %s", hipGetErrorString(e));
+  *gbs = 2.0 * (double)reps * (double)bytes / ((double)ms * 1e-3) / 1e9;
+  return KM_OK;
+}
+
+// k_query and k_children alone over `n` k-mers given on the host: average kernel time over `reps`
+// launches each (HIP events), and how many of the k-mers have count 0.
+extern "C" int km_probe_bench(kmjf_t* h, const uint64_t* kmers, uint64_t n, int reps, double ratio, int64_t n_cutoff,
+                              double* query_ms, double* children_ms, uint64_t* n_zero) {
+  if (!h || !kmers || !n || reps < 1 || !query_ms || !children_ms) return fail(KM_E_ARG, "bad argument");
+  if (!h->d_slots) return fail(KM_E_STATE, "table not uploaded");
+  HIPCHK(hipSetDevice(h->device));
+  DevBuf<uint64_t> dk;
+  DevBuf<uint32_t> dq, dc;
+  DevBuf<uint8_t> dm;
+  Event ev[3];
+  if (dk.alloc(n) != KM_OK || dq.alloc(n) != KM_OK || dm.alloc(n) != KM_OK || dc.alloc(4 * n) != KM_OK) {
+    const std::string why = km_last_error();
+    return fail(KM_E_HIP, "probe benchmark failed: %s", why.c_str());
+  }
+  int rc = KM_OK;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i].h);
+  if (e == hipSuccess) e = hipMemcpy(dk, kmers, n * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    for (int w = 0; w < 2 && rc == KM_OK; ++w) {
+      rc = kmjf_query_batch_dev(h, dk, n, dq, nullptr);
+      if (rc == KM_OK) rc = kmjf_children_batch_dev(h, dk, n, ratio, n_cutoff, 1, dm, dc, nullptr);
+    }
+    if (rc == KM_OK) e = hipDeviceSynchronize();
+    if (rc == KM_OK && e == hipSuccess) e = hipEventRecord(ev[0], nullptr);
+    for (int i = 0; i < reps && rc == KM_OK; ++i) rc = kmjf_query_batch_dev(h, dk, n, dq, nullptr);
+    if (rc == KM_OK && e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
+    for (int i = 0; i < reps && rc == KM_OK; ++i) rc = kmjf_children_batch_dev(h, dk, n, ratio, n_cutoff, 1, dm, dc, nullptr);
+    if (rc == KM_OK && e == hipSuccess) e = hipEventRecord(ev[2], nullptr);
+    if (rc == KM_OK && e == hipSuccess) e = hipEventSynchronize(ev[2]);
+    float q = 0, c = 0;
+    if (rc == KM_OK && e == hipSuccess) e = hipEventElapsedTime(&q, ev[0], ev[1]);
+    if (rc == KM_OK && e == hipSuccess) e = hipEventElapsedTime(&c, ev[1], ev[2]);
+    *query_ms = q / reps;
+    *children_ms = c / reps;
+    if (rc == KM_OK && e == hipSuccess && n_zero) {
+      std::vector<uint32_t> hq(n);
+      e = hipMemcpy(hq.data(), dq, n * 4, hipMemcpyDeviceToHost);
+      uint64_t z = 0;
+      for (uint32_t v : hq) z += v == 0;
+      *n_zero = z;
+    }
+  }
+  if (rc != KM_OK) return rc;
+  if (e != hipSuccess) return fail(KM_E_HIP, "probe benchmark failed: %s", hipGetErrorString(e));
+  return KM_OK;
+}
+
+// Diagnostics: the device counters of the last run — [0] flagged targets (k_seed), [1] unflagged
+// targets k_graph_pure handed to k_graph, [2] flagged targets the epilogue of k_dfs left to k_graph.
+// What the reference logs with -v from inside the walk and the graph (km/utils/MutationFinder.py:160-161,
+// km/utils/Graph.py:198, 231), for the last run: per target the reference edges stripped and the edges kept, and the
+// walk's loop breaks as {target, node index} pairs in walk order.  Any output may be NULL.
+extern "C" int km_batch_graph_log(km_batch_t* b, uint32_t* removed_ref_edges, uint32_t* nonref_edges,
+                                  uint32_t* n_loop_breaks, uint32_t* loop_pairs, uint32_t loop_cap) {
+  if (!b) return fail(KM_E_ARG, "null argument");
+  if (!b->ran_walk) return fail(KM_E_STATE, "no run to report on");
+  // a delivered run: finish it (large tier, pools) first
+  KMCHK(b->out.deliver_pending || b->out.result_ready ? finish_result(b, false) : km_batch_sync(b));
+  HIPCHK(hipSetDevice(b->device));
+  hipStream_t st = b->last_stream;
+  HIPCHK(hipStreamSynchronize(st));
+  const uint32_t n = b->n_targets;
+  if (removed_ref_edges && n) HIPCHK(hipMemcpy(removed_ref_edges, b->log.d_t_eremoved.p, 4ull * n, hipMemcpyDeviceToHost));
+  if (nonref_edges && n) HIPCHK(hipMemcpy(nonref_edges, b->log.d_t_enonref.p, 4ull * n, hipMemcpyDeviceToHost));
+  uint32_t n_loops = 0;
+  if (n) HIPCHK(hipMemcpy(&n_loops, b->log.d_loop_ctl.p, 4, hipMemcpyDeviceToHost));
+  if (n_loop_breaks) *n_loop_breaks = n_loops;
+  const uint32_t have = std::min<uint32_t>(std::min<uint32_t>(n_loops, LOOP_LOG_CAP), loop_cap);
+  if (loop_pairs && have) HIPCHK(hipMemcpy(loop_pairs, b->log.d_loop_list.p, 8ull * have, hipMemcpyDeviceToHost));
+  return KM_OK;
+}
+
+extern "C" int km_batch_debug_counts(km_batch_t* b, uint32_t* out4) {
+  if (!b || !out4) return fail(KM_E_ARG, "null argument");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->last_stream));
+  HIPCHK(hipMemcpy(out4, b->t.d_nflagged.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return KM_OK;
+}
+
+extern "C" int km_batch_timings(km_batch_t* b, float* ms8) {
+  float* ms3 = ms8;
+  if (!b || !ms3) return fail(KM_E_ARG, "null argument");
+  if (!b->synced) {
+    // timing events only: no status pull, no large tier (finish_result does that when asked)
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->last_stream));
+    read_timings(b);
+  }
+  for (int i = 0; i < 8; ++i) ms3[i] = b->tm.ms[i];
+  return KM_OK;
+}
+
+extern "C" int km_batch_sizes(km_batch_t* b, km_batch_sizes_t* s) {
+  if (!b || !s) return fail(KM_E_ARG, "null argument");
+  KMCHK(finish_result(b, true));          // the sizes km_batch_fetch fills: a full delivery
+  sizes_of_result(b, s);
+  return KM_OK;
+}
+
+// Copying variant of km_batch_result: fills caller-allocated arrays (sizes from km_batch_sizes).
+// node_kmer, when asked for, is rebuilt here: the target's own k-mers from the packed targets,
+// the walk-discovered ones from extra_kmer.
+extern "C" int km_batch_fetch(km_batch_t* b, const km_batch_out_t* out) {
+  if (!b || !out) return fail(KM_E_ARG, "null argument");
+  KMCHK(finish_result(b, true));          // the copying API always returns every node
+  km_batch_out_t v;
+  km_batch_sizes_t s;
+  view_of_result(b, &v);
+  sizes_of_result(b, &s);
+  const uint32_t n = b->n_targets;
+  if (out->status) memcpy(out->status, v.status, 4ull * n);
+  if (out->aux) memset(out->aux, 0, 4ull * n);
+  if (out->n_ref) memcpy(out->n_ref, v.n_ref, 4ull * n);
+  if (out->probes) memcpy(out->probes, v.probes, 8ull * n);
+  if (out->node_off) memcpy(out->node_off, v.node_off, 8ull * (n + 1));
+  if (out->extra_off) memcpy(out->extra_off, v.extra_off, 8ull * (n + 1));
+  if (out->node_count) memcpy(out->node_count, v.node_count, 4 * s.n_nodes);
+  if (out->extra_kmer) memcpy(out->extra_kmer, v.extra_kmer, 8 * s.n_extra);
+  if (out->path_off) memcpy(out->path_off, v.path_off, 4ull * (n + 1));
+  if (out->ref_max_cov) memcpy(out->ref_max_cov, v.ref_max_cov, 4ull * n);
+  if (out->run_off) memcpy(out->run_off, v.run_off, 8ull * (s.n_paths + 1));
+  if (out->run_start) memcpy(out->run_start, v.run_start, 4 * s.n_runs);
+  if (out->run_len) memcpy(out->run_len, v.run_len, 4 * s.n_runs);
+  if (out->path_len) memcpy(out->path_len, v.path_len, 4ull * s.n_paths);
+  if (out->path_min_cov) memcpy(out->path_min_cov, v.path_min_cov, 4ull * s.n_paths);
+  if (out->node_kmer && n) {
+    HIPCHK(hipSetDevice(b->device));
+    if (b->in.h_packed.empty()) {
+      b->in.h_packed.resize(b->in.h_woff[n]);
+      HIPCHK(hipMemcpy(b->in.h_packed.data(), b->in.d_packed.p, b->in.h_woff[n] * 8, hipMemcpyDeviceToHost));
+    }
+    const int k = b->db->k;
+    for (uint32_t t = 0; t < n; ++t) {
+      const uint64_t a0 = v.node_off[t], cnt = v.node_off[t + 1] - a0;
+      if (!cnt) continue;
+      const uint64_t ne = v.extra_off[t + 1] - v.extra_off[t], nr = cnt - ne;
+      const uint64_t* words = b->in.h_packed.data() + b->in.h_woff[t];
+      uint64_t* dst = out->node_kmer + a0;
+      for (uint64_t i = 0; i < nr; ++i) {
+        const uint64_t w = i >> 5, sh = (i & 31) * 2;
+        const uint64_t x = sh ? ((words[w] << sh) | (words[w + 1] >> (64 - sh))) : words[w];
+        dst[i] = x >> (64 - 2 * k);
+      }
+      memcpy(dst + nr, v.extra_kmer + v.extra_off[t], 8 * ne);
+    }
+  }
+  return KM_OK;
+}

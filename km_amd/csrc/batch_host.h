@@ -576,6 +576,7 @@ static void fill_walk_args(km_batch* b, WalkArgs& a) {
   a.g_stride = 0;
   a.dbg = knobs().debug_flags & 0xFFu;          // timing ablations (diagnostics build only); results are invalid
   a.spec = knobs().speculate ? 1u : 0u;
+  a.pool_counters = b->paths.d_counters.p;
 }
 
 static void fill_graph_args(km_batch* b, GraphArgs& g) {
@@ -926,9 +927,10 @@ struct RunFlags {
         count_fetches(s & KM_RUN_COUNT_FETCHES), timed(s & KM_RUN_TIMED), timed_fine(timed && !(s & KM_RUN_TIMED_STAGES)) {}
 };
 
-// One step.  In stream order: [memset of the path-pool counters] k_pack, k_seed, k_dfs, [k_dfs of the device's large
-// tier], k_graph_pure, k_graph, [k_graph of the device's large tier], then the delivery (enqueue_deliver) when asked
-// for; with KM_RUN_HIPGRAPH everything before the delivery is captured once and replayed.
+// One step.  In stream order: k_pack (which also zeroes the path-pool counters), k_seed, k_dfs, [k_dfs of the device's
+// large tier], k_graph_pure, k_graph, [k_graph of the device's large tier], then the delivery (enqueue_deliver) when
+// asked for; with KM_RUN_HIPGRAPH everything before the delivery is captured once and replayed.  A graph-only run
+// (no k_pack) zeroes the counters with a fill command of its own (launch_graph_fast).
 extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
   if (!b) return fail(KM_E_ARG, "null argument");
   const bool host_trace = knobs().host_trace;      // diagnostics: host time of the sections
@@ -986,9 +988,7 @@ extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
   }
   ht[2] = host_trace ? host_now_us() : 0;
   if (f.stages & KM_STAGE_WALK) {
-    // the path-pool counters of the graph kernels (zeroed here, outside the timed walk stage)
-    HIPCHK(hipMemsetAsync(b->paths.d_counters.p, 0, (POOL_GROUPS * POOL_CTR_STRIDE + 16) * sizeof(unsigned long long), st));
-    ht[3] = host_trace ? host_now_us() : 0;
+    // (the path-pool counters of the graph kernels are zeroed by k_pack: no fill command per step)
     if (b->tm.timed) HIPCHK(hipEventRecord(b->tm.ev[0], st));
     hipLaunchKernelGGL(k_pack, dim3((b->n_targets + PACK_WAVES - 1) / PACK_WAVES), dim3(64 * PACK_WAVES), 0, st, wa);
     if (b->tm.timed && f.timed_fine) HIPCHK(hipEventRecord(b->tm.ev[3], st));
@@ -1045,8 +1045,8 @@ extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
   if (host_trace) ht[4] = host_now_us();
   const int rc_deliver = f.deliver ? enqueue_deliver(b, st, f.lean, f.count16) : KM_OK;
   if (host_trace)
-    fprintf(stderr, "[km host] run: setdevice+layout %.1f us, geometry %.1f, memset %.1f, launches %.1f, delivery %.1f, whole call %.1f\n",
-            ht[1] - ht[0], ht[2] - ht[1], ht[3] - ht[2], ht[4] - ht[3], host_now_us() - ht[4], host_now_us() - ht[0]);
+    fprintf(stderr, "[km host] run: setdevice+layout %.1f us, geometry %.1f, launches %.1f, delivery %.1f, whole call %.1f\n",
+            ht[1] - ht[0], ht[2] - ht[1], ht[4] - ht[2], host_now_us() - ht[4], host_now_us() - ht[0]);
   return rc_deliver;
 }
 

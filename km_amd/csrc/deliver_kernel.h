@@ -114,22 +114,36 @@ __host__ __device__ inline uint64_t out_align(uint64_t v) { return (v + 15) & ~1
 
 struct OutCounts { uint64_t nodes, extra, paths, runs; };
 
-__device__ inline OutCounts out_counts_of(const OutArgs& a, uint32_t t, uint32_t* needs, uint32_t* st_out) {
-  const uint32_t st = a.status[t];
-  const uint32_t gs = a.ran_graph ? a.g_status[t] : T_OK;
+// The ten words k_out_scan needs of a target.  Every array holds max_targets entries, so all of them are requested
+// at once, whatever the statuses turn out to be (they used to follow one another behind the branches on the
+// statuses: three to four dependent round trips); what a stage that did not run left there is never selected.
+struct OutWords {
+  uint32_t status, g_status, n_nodes, n_ref, n_paths, n_runs, ref_max;
+  unsigned long long probes, dfs_probes, fetches;
+};
+__device__ inline OutWords out_words_of(const OutArgs& a, uint32_t t) {
+  OutWords w;
+  w.status = a.status[t]; w.g_status = a.g_status[t]; w.n_nodes = a.n_nodes[t]; w.n_ref = a.n_ref[t];
+  w.n_paths = a.t_npaths[t]; w.n_runs = a.t_nruns[t]; w.ref_max = a.t_refmax[t];
+  w.probes = a.probes[t]; w.dfs_probes = a.dfs_probes[t]; w.fetches = a.fetches[t];
+  return w;
+}
+
+__device__ inline OutCounts out_counts_of(const OutArgs& a, const OutWords& w, uint32_t* needs, uint32_t* st_out) {
+  const uint32_t st = w.status;
+  const uint32_t gs = a.ran_graph ? w.g_status : T_OK;
   OutCounts c = {0, 0, 0, 0};
   if (st == T_NEEDS_BIG || (st == T_OK && gs == T_NEEDS_BIG)) *needs = 1;
   if (st == T_OK || st == T_NODE_LIMIT) {
-    c.nodes = a.n_nodes[t];
-    const uint32_t nr = a.n_ref[t];
-    c.extra = c.nodes > nr ? c.nodes - nr : 0;
+    c.nodes = w.n_nodes;
+    c.extra = c.nodes > w.n_ref ? c.nodes - w.n_ref : 0;
   }
   if (a.ran_graph && st == T_OK && gs == T_OK) {
-    c.paths = a.t_npaths[t];
-    c.runs = a.t_nruns[t];
+    c.paths = w.n_paths;
+    c.runs = w.n_runs;
     // lean delivery: a bare-reference target is fully described by its path record
     // (path_min_cov) and ref_max_cov; its counts stay on the device
-    if (a.lean && c.paths == 1 && a.t_refmax[t] != NOT_BARE) c.nodes = 0;
+    if (a.lean && c.paths == 1 && w.ref_max != NOT_BARE) c.nodes = 0;
   }
   *st_out = (st == T_OK && gs != T_OK) ? T_INTERNAL : st;
   return c;
@@ -151,14 +165,14 @@ __global__ __launch_bounds__(OUT_SCAN_THREADS) void k_out_scan(OutArgs a) {
   uint32_t needs = 0;
   if (t < n) {
     uint32_t st;
-    const OutCounts c = out_counts_of(a, t, &needs, &st);
+    const OutWords w = out_words_of(a, t);                 // one round trip; everything below selects in registers
+    const OutCounts c = out_counts_of(a, w, &needs, &st);
     s[0] = c.nodes; s[1] = c.extra; s[2] = c.paths; s[3] = c.runs;
-    const unsigned long long sp = a.probes[t], dp = a.dfs_probes[t];
-    seedp = sp; probes = sp + dp; fetches = a.count_fetches ? a.fetches[t] : 0ull;
+    seedp = w.probes; probes = w.probes + w.dfs_probes; fetches = a.count_fetches ? w.fetches : 0ull;
     a.o_status[t] = st;
-    a.o_nref[t] = a.n_ref[t];
-    a.o_probes[t] = sp + dp;
-    a.o_refmax[t] = a.ran_graph ? a.t_refmax[t] : NOT_BARE;
+    a.o_nref[t] = w.n_ref;
+    a.o_probes[t] = w.probes + w.dfs_probes;
+    a.o_refmax[t] = a.ran_graph ? w.ref_max : NOT_BARE;
   }
   // exclusive scan of the four sizes over the block: within the wave, then across the waves
   unsigned long long ex[4];
@@ -210,14 +224,20 @@ __global__ __launch_bounds__(OUT_SCAN_THREADS) void k_out_scan(OutArgs a) {
   if (!last_flag || wave != 0) return;
   // The block that finishes last turns the block totals into exclusive prefixes (one wave, 64
   // blocks per round) so that k_out_pack finds its base with two loads instead of a reduction.
+  // Acquire side of the ticket: lane 0's atomicAdd saw every other block's ticket, each behind that block's fence;
+  // this fence stands between it and the plain loads of their totals below.
+  __threadfence();
   const uint32_t nblk = gridDim.x;
   unsigned long long carry[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (uint32_t b0 = 0; b0 < nblk; b0 += 64) {
     const uint32_t bq = b0 + lane;
-    unsigned long long v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-      v[q] = bq < nblk ? __hip_atomic_load(a.blk_tot + 8ull * bq + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+    unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (bq < nblk) {                                       // a block's 64-byte row: two 32-byte loads
+      const ulonglong4* B = reinterpret_cast<const ulonglong4*>(a.blk_tot + 8ull * bq);
+      const ulonglong4 b0v = B[0], b1v = B[1];
+      v[0] = b0v.x; v[1] = b0v.y; v[2] = b0v.z; v[3] = b0v.w;
+      v[4] = b1v.x; v[5] = b1v.y; v[6] = b1v.z; v[7] = b1v.w;
+    }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       unsigned long long inc = v[q];
@@ -258,6 +278,56 @@ __device__ inline bool rle_less(const uint32_t* sa, const uint32_t* la, uint32_t
   return ia == na && ib < nb;
 }
 
+// A count as its 16-bit delivery: a value >= 65535 goes, exact, on the escape list under its global node index.
+__device__ inline uint32_t out_clip16(const OutArgs& a, uint32_t v, uint64_t node) {
+  if (v >= 0xFFFFu) {
+    const unsigned long long at = atomicAdd(&a.totals[OT_N_ESC], 1ull);
+    if (at < OUT_ESC_CAP) { a.o_esc_node[at] = node; a.o_esc_value[at] = v; }
+    v = 0xFFFFu;
+  }
+  return v;
+}
+
+// The counts of one target, src[0 .. nn) -> node_count[n0 .. n0 + nn), by one wave.  Whole 16-byte groups of the
+// source go as one load per lane, two of them in flight (`src_mis`: elements by which src is past a 16-byte boundary);
+// a group is stored as one word where its destination is aligned for it, element by element otherwise.  The at most
+// 3 + 3 elements in front of the first and behind the last whole group are copied one by one.
+template <bool C16>
+__device__ inline void out_copy_counts(const OutArgs& a, const uint32_t* src, uint32_t src_mis, void* dst_base,
+                                       uint64_t n0, uint32_t nn, uint32_t lane) {
+  uint16_t* d16 = reinterpret_cast<uint16_t*>(dst_base) + n0;
+  uint32_t* d32 = reinterpret_cast<uint32_t*>(dst_base) + n0;
+  const uint32_t head = min(nn, (4u - src_mis) & 3u);
+  const uint32_t ngrp = (nn - head) / 4;
+  const uint32_t rest = head + 4 * ngrp;                   // first element behind the whole groups
+  if (lane < head + (nn - rest)) {
+    const uint32_t i = lane < head ? lane : rest + (lane - head);
+    const uint32_t v = src[i];
+    if (C16) d16[i] = (uint16_t)out_clip16(a, v, n0 + i); else d32[i] = v;
+  }
+  const uint4* src4 = reinterpret_cast<const uint4*>(src + head);
+  const bool wide = ((n0 + head) & 3u) == 0;               // the groups' destinations are 8-byte (16-bit counts) / 16-byte aligned
+  for (uint32_t g0 = lane; g0 < ngrp; g0 += 128) {
+    uint4 v[2];
+#pragma unroll
+    for (uint32_t u = 0; u < 2; ++u) v[u] = (g0 + 64 * u < ngrp) ? src4[g0 + 64 * u] : make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (uint32_t u = 0; u < 2; ++u) {
+      if (g0 + 64 * u >= ngrp) continue;
+      const uint32_t i = head + 4 * (g0 + 64 * u);
+      if (C16) {
+        const uint32_t x = out_clip16(a, v[u].x, n0 + i), y = out_clip16(a, v[u].y, n0 + i + 1);
+        const uint32_t z = out_clip16(a, v[u].z, n0 + i + 2), w = out_clip16(a, v[u].w, n0 + i + 3);
+        if (wide) *reinterpret_cast<uint2*>(d16 + i) = make_uint2(x | (y << 16), z | (w << 16));
+        else { d16[i] = (uint16_t)x; d16[i + 1] = (uint16_t)y; d16[i + 2] = (uint16_t)z; d16[i + 3] = (uint16_t)w; }
+      } else {
+        if (wide) *reinterpret_cast<uint4*>(d32 + i) = v[u];
+        else { d32[i] = v[u].x; d32[i + 1] = v[u].y; d32[i + 2] = v[u].z; d32[i + 3] = v[u].w; }
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(64) void k_out_pack(OutArgs a) {
   const uint32_t t = blockIdx.x;
   const uint32_t lane = threadIdx.x & 63u;
@@ -267,11 +337,11 @@ __global__ __launch_bounds__(64) void k_out_pack(OutArgs a) {
   const uint32_t nblk = (n + OUT_SCAN_THREADS - 1) / OUT_SCAN_THREADS, myblk = t / OUT_SCAN_THREADS;
   // every word that depends on the target alone is requested here, with the block bases (they used to follow
   // one another behind the offsets: five dependent round trips per wave, most of a wave's 3.5 us)
-  const ulonglong4 lc = reinterpret_cast<const ulonglong4*>(a.loc)[t];
   const uint4 ct = reinterpret_cast<const uint4*>(a.cnt)[t];
-  const uint64_t nb = a.node_base[t];
   const uint32_t pb = a.t_pathbase[t];
   const unsigned long long pool_ovf = a.ran_graph ? *a.pool_overflow : 0ull;
+  const ulonglong4 lc = reinterpret_cast<const ulonglong4*>(a.loc)[t];
+  const uint64_t nb = a.node_base[t];
   unsigned long long pre[4], tot[8];
   {
     const ulonglong4 bb = *reinterpret_cast<const ulonglong4*>(a.blk_base + 4ull * myblk);
@@ -280,6 +350,16 @@ __global__ __launch_bounds__(64) void k_out_pack(OutArgs a) {
     pre[0] = bb.x; pre[1] = bb.y; pre[2] = bb.z; pre[3] = bb.w;
     tot[0] = g0.x; tot[1] = g0.y; tot[2] = g0.z; tot[3] = g0.w;
     tot[4] = g1.x; tot[5] = g1.y; tot[6] = g1.z; tot[7] = g1.w;
+  }
+  // a target with exactly one path (99 % of a typical batch; the whole result of a lean bare-reference target): its
+  // path record and its first 64 runs are requested as soon as `pb` is here, ahead of the count copies they used to
+  // follow.  (ct.z == 1: the graph stage answered this target, so `pb` is its record; after a pool overflow nothing is
+  // packed and no record is trusted)
+  uint32_t nr1 = 0, plen1 = 0, pmin1 = 0, rs1 = 0, rl1 = 0;
+  uint64_t rb1 = 0;
+  if (ct.z == 1 && !pool_ovf) {
+    nr1 = a.p_nruns[pb]; rb1 = a.p_runbase[pb]; plen1 = a.p_len[pb]; pmin1 = a.p_mincov[pb];
+    if (lane < nr1) { rs1 = a.r_start[rb1 + lane]; rl1 = a.r_len[rb1 + lane]; }
   }
   uint64_t o = 0;
   const uint64_t off_count = o;  o = out_align(o + (a.count16 ? 2 : 4) * tot[0]);
@@ -320,36 +400,9 @@ __global__ __launch_bounds__(64) void k_out_pack(OutArgs a) {
   uint64_t* o_roff = reinterpret_cast<uint64_t*>(a.tail + off_runoff);
   uint32_t* o_rs = reinterpret_cast<uint32_t*>(a.tail + off_rstart);
   uint32_t* o_rl = reinterpret_cast<uint32_t*>(a.tail + off_rlen);
-  // ---- nodes (four independent loads per lane in flight)
-  if (a.count16) {
-    const uint32_t* src = a.node_cnt + nb;
-    uint16_t* dst = reinterpret_cast<uint16_t*>(a.tail + off_count) + n0;
-    for (uint32_t i0 = lane; i0 < nn; i0 += 256) {
-      uint32_t v[4];
-#pragma unroll
-      for (uint32_t u = 0; u < 4; ++u) v[u] = (i0 + 64 * u < nn) ? src[i0 + 64 * u] : 0u;
-#pragma unroll
-      for (uint32_t u = 0; u < 4; ++u) {
-        if (i0 + 64 * u >= nn) continue;
-        if (v[u] >= 0xFFFFu) {                              // the exact value goes on the escape list
-          const unsigned long long at = atomicAdd(&a.totals[OT_N_ESC], 1ull);
-          if (at < OUT_ESC_CAP) { a.o_esc_node[at] = n0 + i0 + 64 * u; a.o_esc_value[at] = v[u]; }
-          v[u] = 0xFFFFu;
-        }
-        dst[i0 + 64 * u] = (uint16_t)v[u];
-      }
-    }
-  } else {
-    const uint32_t* src = a.node_cnt + nb;
-    uint32_t* dst = o_cnt + n0;
-    for (uint32_t i0 = lane; i0 < nn; i0 += 256) {
-      uint32_t v[4];
-#pragma unroll
-      for (uint32_t u = 0; u < 4; ++u) v[u] = (i0 + 64 * u < nn) ? src[i0 + 64 * u] : 0u;
-#pragma unroll
-      for (uint32_t u = 0; u < 4; ++u) if (i0 + 64 * u < nn) dst[i0 + 64 * u] = v[u];
-    }
-  }
+  // ---- nodes (16-byte loads, two per lane in flight)
+  if (a.count16) out_copy_counts<true>(a, a.node_cnt + nb, (uint32_t)(nb & 3u), a.tail + off_count, n0, nn, lane);
+  else out_copy_counts<false>(a, a.node_cnt + nb, (uint32_t)(nb & 3u), o_cnt, n0, nn, lane);
   if (ne) {
     const uint64_t* src = a.node_kmer + nb + (nn - ne);
     uint64_t* dst = o_ext + e0;
@@ -359,10 +412,9 @@ __global__ __launch_bounds__(64) void k_out_pack(OutArgs a) {
   // ---- paths, sorted by index sequence
   if (np == 0) return;
   if (np == 1) {
-    const uint32_t nr = a.p_nruns[pb];
-    const uint64_t rb = a.p_runbase[pb];
-    if (lane == 0) { o_plen[p0] = a.p_len[pb]; o_pmin[p0] = a.p_mincov[pb]; o_roff[p0] = cur; }
-    for (uint32_t q = lane; q < nr; q += 64) { o_rs[cur + q] = a.r_start[rb + q]; o_rl[cur + q] = a.r_len[rb + q]; }
+    if (lane == 0) { o_plen[p0] = plen1; o_pmin[p0] = pmin1; o_roff[p0] = cur; }
+    if (lane < nr1) { o_rs[cur + lane] = rs1; o_rl[cur + lane] = rl1; }
+    for (uint32_t q = lane + 64; q < nr1; q += 64) { o_rs[cur + q] = a.r_start[rb1 + q]; o_rl[cur + q] = a.r_len[rb1 + q]; }
     return;
   }
   for (uint32_t i = lane; i < np; i += 64) {

@@ -169,6 +169,9 @@ struct WalkArgs {
   unsigned char* f_ws;  // fast tier: global scratch for the DFS stack frames (per block)
   uint64_t f_stride;
   unsigned long long* stamps;  // diagnostics (KM_SEED_STAMPS): 16 words per k_seed wave, else null
+  // the path-pool counters of the graph stage (POOL_GROUPS * POOL_CTR_STRIDE + 16 words): k_pack, the first kernel of
+  // a step, zeroes them — everything that reads or adds to them is a later kernel of the same stream
+  unsigned long long* pool_counters;
 };
 
 // Per-target k_dfs state.  BIG tier: everything in one global block.  Fast tier: node
@@ -369,6 +372,15 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void k_pack(WalkArgs a) {
     if (t == 0) a.loop_ctl[0] = 0;
     if (t == 0 && a.big_ctl) { a.big_ctl[0] = 0; a.big_ctl[1] = 0; }
     if (t == 0) { a.n_flagged[0] = 0; a.n_flagged[1] = 0; a.n_flagged[2] = 0; }   // [1]: targets k_graph_pure hands to k_graph, [2]: those k_dfs's epilogue leaves to it
+  }
+  // the path-pool counters start every step at zero (a fill command of its own used to stand in front of this kernel
+  // in every step): 16-byte stores, wave t the pairs t * 64 .. t * 64 + 63, behind the wave's own work.  (In front of
+  // the wave's loads they cost the kernel the same: DESIGN.md section 5, round 5.)
+  {
+    constexpr uint32_t CTR_PAIRS = (POOL_GROUPS * POOL_CTR_STRIDE + 16) / 2;
+    ulonglong2* ctr = reinterpret_cast<ulonglong2*>(a.pool_counters);
+    for (uint64_t i = (uint64_t)t * 64 + lane; i < CTR_PAIRS; i += (uint64_t)a.n_targets * 64)
+      ctr[i] = make_ulonglong2(0ull, 0ull);
   }
 }
 

@@ -407,6 +407,40 @@ int km_counter_destroy(km_counter_t* c);
 int km_text_strip(km_text_state_t* st, const char* text, uint64_t n, int final, uint8_t* out, uint64_t cap,
                   uint64_t* n_out, uint64_t* consumed);
 
+/* ---- files in Jellyfish's own record order ------------------------------------------------------
+ * Real Jellyfish orders the records of a `binary/sorted` file by pos(key) = M . key over GF(2) — M is the
+ * header's matrix1: r rows, c = 2k columns, bit i of the key (0 = least significant) selects columns[c-1-i],
+ * the result is masked with size - 1 — and binary-searches that order; ties are ordered by key (DESIGN.md 10,
+ * "File, Jellyfish order").  The functions below sort records that way on the GPU and write such files. */
+/* Host only.  A deterministic matrix of r = size_log2 rows and 2k columns with full row rank, made from a seeded
+ * mixer (reseeded until the rank is full).  KM_E_K for k outside 2..32, KM_E_ARG unless 1 <= size_log2 <= 2k. */
+int km_jf_matrix(int k, int size_log2, uint64_t seed, uint64_t* columns /* [2k] */);
+/* Host arrays in and out: records[n * (ceil(2k/8) + 4)] receives the file records ([little-endian key bytes]
+ * [4 count bytes]) in (pos, key) order under the caller's matrix, pos_or_null[n] their positions in that order.
+ * The keys are expected to be distinct (records with one key have no defined order among themselves).  n == 0
+ * returns KM_OK without a launch; KM_E_ARG for n >= 2^32 (32-bit bucket directory) and, like KM_E_K, for the
+ * shapes km_jf_matrix refuses, before any HIP call.  stream: a hipStream_t, NULL = one of the library's own. */
+int km_jf_sort_records(int device, const uint64_t* columns, int k, int size_log2, const uint64_t* keys,
+                       const uint32_t* counts, uint64_t n, uint8_t* records, uint64_t* pos_or_null, void* stream);
+/* The last sort of the calling thread (km_jf_sort_records, km_counter_write_jf): out4[0] buckets, [1] entries of
+ * the largest bucket, [2] buckets too large for the sort in LDS (sorted in global memory instead), [3] 0. */
+int km_jf_sort_stats(uint64_t* out4);
+/* ... and the time of its kernels (position, scan, scatter, sort), measured with HIP events on its stream. */
+int km_jf_sort_kernel_ms(float* ms);
+/* Host only.  The header of a file of n records in this order — 9 digits, JSON with sorted keys, padding to 8
+ * bytes — with size = the power of two >= max(16, 2n), at most 4^k, and matrix1 = km_jf_matrix(k, log2 size,
+ * seed), both also returned.  cmdline_json: a JSON array, NULL = ["km_amd","count"]; it is pasted into the header
+ * as it is, so the caller answers for its being valid JSON — only its brackets are checked (KM_E_ARG unless it
+ * begins with '[' and ends with ']').  out == NULL asks for *len only; KM_E_CAPACITY if cap < *len. */
+int km_jf_header(int k, int canonical, uint64_t n, uint64_t seed, const char* cmdline_json, char* out,
+                 uint64_t cap, uint64_t* len, uint64_t* columns /* [2k] */, int* size_log2);
+/* After km_counter_finish (KM_E_STATE before): sort the device-resident records, write the km_jf_header of
+ * (k, canonical, n, seed, cmdline_json) and the records to `path`.  The records never visit the host as arrays:
+ * the finished file bytes are drained through the counter's pinned staging buffers piece by piece.  The file is
+ * created before anything runs on the device: KM_E_IO if it cannot be created or written, and whenever the call
+ * fails after that the partial file is removed. */
+int km_counter_write_jf(km_counter_t* c, const char* path, const char* cmdline_json, uint64_t seed);
+
 /* ---- measurement helpers (bench.py at N = 1 holds no device buffers of its own) ------------- */
 int km_device_sync(int device);                                    /* hipDeviceSynchronize on `device`          */
 /* device-to-device copy of `bytes` bytes, `reps` times: read + write GB/s (the box's large-copy

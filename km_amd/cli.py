@@ -291,23 +291,29 @@ def main_min_cov(args, out=None):
 
 def main_count(args, err=None):
     """`jellyfish count -m K [-C] -L N -s SIZE -o OUT reads..` on the GPU (km_amd.count): the k-mers of the read
-    files counted on the device, the records with count >= -L written to OUT (read by every tool here; real
-    Jellyfish could not query the file, see km_amd.count.write_records)."""
+    files counted on the device, the records with count >= -L written to OUT (read by every tool here).  The file
+    is sorted by key, which real Jellyfish could not query (km_amd.count.write_records); with --jellyfish-order
+    it is sorted on the device into Jellyfish's own record order and written from there (Counter.write_jf)."""
     err = sys.stderr if err is None else err
     from . import count as kc
     db, stats, counter = kc.count_files(args.reads, k=args.mer_len, canonical=args.canonical,
                                         lower_count=args.lower_count, device=default_device(),
                                         expected_distinct=args.size, keep_counter=True)
+    cmdline = ["km_amd", "count", "-m", str(args.mer_len)] + (["-C"] if args.canonical else []) + [
+        "-L", str(args.lower_count), "-s", str(args.size)] + (
+        ["--jellyfish-order"] if args.jellyfish_order else []) + ["-o", args.output] + list(args.reads)
     try:
-        keys, counts = counter.records()
+        if args.jellyfish_order:
+            counter.write_jf(args.output, cmdline=cmdline)
+        else:
+            keys, counts = counter.records()
     finally:
         counter.close()
         db.close()
     for key in ("bases", "kmers", "distinct", "slots", "n_grow"):
         err.write("#%s:%d\n" % (key, stats[key]))
-    cmdline = ["km_amd", "count", "-m", str(args.mer_len)] + (["-C"] if args.canonical else []) + [
-        "-L", str(args.lower_count), "-s", str(args.size), "-o", args.output] + list(args.reads)
-    kc.write_records(args.output, keys, counts, args.mer_len, args.canonical, cmdline=cmdline)
+    if not args.jellyfish_order:
+        kc.write_records(args.output, keys, counts, args.mer_len, args.canonical, cmdline=cmdline)
 
 
 def main(argv=None):
@@ -336,6 +342,8 @@ def main(argv=None):
     ct.add_argument("-L", "--lower-count", type=int, default=1, help="don't output k-mers with count < lower-count")
     ct.add_argument("-s", "--size", type=int, default=0, help="expected number of distinct k-mers (0: grow as needed)")
     ct.add_argument("-o", "--output", default="mer_counts.jf", help="output file (default: mer_counts.jf)")
+    ct.add_argument("--jellyfish-order", action="store_true",
+                    help="write the records in Jellyfish's own order (matrix position, then key), sorted on the GPU")
     ct.add_argument("reads", nargs="+", help="FASTA or FASTQ files, plain or gzip; - is stdin")
     args = parser.parse_args(argv)
     cmd = args._cmd

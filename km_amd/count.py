@@ -3,7 +3,9 @@ front of every km tool (``python -m km_amd count``).
 
 ``count_files`` streams FASTA / FASTQ files (plain or gzip) through :class:`km_amd.lib.Counter` and returns the
 database built on the device from the counted records; ``write_records`` writes such records in the file
-framing the readers of this project load.  Only the standard library and numpy.
+framing the readers of this project load, sorted by key; ``write_jellyfish`` writes them in Jellyfish's own
+record order (sorted on the GPU), as ``Counter.write_jf`` does for records still on the device.  Only the
+standard library and numpy.
 """
 
 import gzip
@@ -75,7 +77,8 @@ def write_records(path, keys, counts, k, canonical, cmdline=None):
     whatever order they arrive in.
 
     Real Jellyfish orders the records of such a file by its matrix hash and binary-searches that order; it
-    could not query this file.  Readers that load all records (every reader here) do not care."""
+    could not query this file (write_jellyfish writes that order).  Readers that load all records (every reader
+    here) do not care."""
     keys = np.ascontiguousarray(keys, dtype=np.uint64)
     counts = np.ascontiguousarray(counts, dtype=np.uint32)
     if keys.shape != counts.shape or keys.ndim != 1:
@@ -106,4 +109,23 @@ def write_records(path, keys, counts, k, canonical, cmdline=None):
     with open(path, "wb") as fh:
         fh.write(b"%09d" % len(text))
         fh.write(text)
+        fh.write(rec.tobytes())
+
+
+def write_jellyfish(path, keys, counts, k, canonical, cmdline=None, seed=0, device=0):
+    """Write host-resident (keys, counts) as a `binary/sorted` file in Jellyfish's own record order: ascending
+    pos = matrix1 . key over GF(2), ties by key ("File, Jellyfish order").  The header (size,
+    matrix1 from `seed`, the keys of a real Jellyfish header minus the informational ones) comes from the
+    library's own writer and the records are sorted on the GPU, so the file equals, byte for byte, what
+    Counter.write_jf writes for the same records, cmdline and seed."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if keys.shape != counts.shape or keys.ndim != 1:
+        raise ValueError("keys and counts must be 1-d arrays of one length")
+    if not 2 <= int(k) <= 32:
+        raise ValueError("k=%d unsupported" % k)
+    header, columns, size_log2 = _lib.jf_header(k, canonical, keys.size, cmdline=cmdline, seed=seed)
+    rec = _lib.jf_sort_records(columns, k, size_log2, keys, counts, device=device)
+    with open(path, "wb") as fh:
+        fh.write(header)
         fh.write(rec.tobytes())

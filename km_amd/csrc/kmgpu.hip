@@ -7,6 +7,7 @@
 //   result_host.h  reading a delivered step: km_batch_result / _pump / _fetch, diagnostics and measurement exports
 //   kmin_host.h    km_linear_kmin
 //   count_host.h   km_counter_*, km_text_strip
+//   jf_order_host.h  km_jf_*, km_counter_write_jf: files in Jellyfish's own record order
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 #include <sys/mman.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +34,7 @@
 #include "device_common.h"
 #include "fastx_strip.h"
 #include "graph_kernel.h"
+#include "jf_order_kernel.h"
 #include "jf_reader.h"
 #include "kmin_kernel.h"
 #include "table_kernels.h"
@@ -45,3 +48,4 @@ using namespace kmd;
 #include "result_host.h"
 #include "kmin_host.h"
 #include "count_host.h"
+#include "jf_order_host.h"

@@ -7,6 +7,7 @@ is missing or cannot be loaded, :func:`load` raises.
 
 import atexit
 import ctypes as C
+import json
 import os
 import sys
 import weakref
@@ -36,6 +37,8 @@ SYMBOLS = [
     "km_report_rows", "km_report_free", "km_linear_kmin", "km_strerror", "km_last_error",
     "km_counter_create", "km_counter_add_bases", "km_counter_add_text", "km_counter_stats", "km_counter_finish",
     "km_counter_records", "km_counter_destroy", "km_text_strip",
+    "km_jf_matrix", "km_jf_sort_records", "km_jf_sort_stats", "km_jf_sort_kernel_ms", "km_jf_header",
+    "km_counter_write_jf",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
 ]
 
@@ -226,6 +229,12 @@ def load():
         "km_counter_records": [vp, vp, vp, u64, C.POINTER(u64)],
         "km_counter_destroy": [vp],
         "km_text_strip": [C.POINTER(TextState), vp, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(u64)],
+        "km_jf_matrix": [i32, i32, u64, vp],
+        "km_jf_sort_records": [i32, vp, i32, i32, vp, vp, u64, vp, vp, vp],
+        "km_jf_sort_stats": [vp],
+        "km_jf_sort_kernel_ms": [C.POINTER(C.c_float)],
+        "km_jf_header": [i32, i32, u64, u64, cp, vp, u64, C.POINTER(u64), vp, C.POINTER(i32)],
+        "km_counter_write_jf": [vp, cp, cp, u64],
         "km_device_count": [C.POINTER(i32)],
         "km_device_sync": [i32],
         "km_device_copy_GBs": [i32, u64, i32, C.POINTER(dbl)],
@@ -501,6 +510,61 @@ class Counter:
         if n.value:
             check(self._lib.km_counter_records(self._c, ptr(keys), ptr(counts), n.value, C.byref(n)))
         return keys, counts
+
+    def write_jf(self, path, cmdline=None, seed=0):
+        """km_counter_write_jf: the finished counter's records as a file in Jellyfish's own record order, sorted
+        on the device and written natively (the records are not copied to the host as arrays)."""
+        check(self._lib.km_counter_write_jf(self._c, os.fsencode(path), _cmdline_json(cmdline), int(seed)))
+
+
+def _cmdline_json(cmdline):
+    return None if cmdline is None else json.dumps([str(a) for a in cmdline], separators=(",", ":")).encode("ascii")
+
+
+def jf_matrix(k, size_log2, seed=0):
+    """km_jf_matrix: the 2k column words of a deterministic full-rank matrix with size_log2 rows (host only)."""
+    columns = np.zeros(64, np.uint64)                 # (room whatever k is: a bad k is the library's to refuse)
+    check(load().km_jf_matrix(int(k), int(size_log2), int(seed), ptr(columns)))
+    return columns[:2 * int(k)].copy()
+
+
+def jf_header(k, canonical, n, cmdline=None, seed=0):
+    """km_jf_header -> (header bytes, columns, size_log2) of a file of n records in Jellyfish's order."""
+    lib = load()
+    columns = np.zeros(64, np.uint64)
+    ln, s = C.c_uint64(), C.c_int()
+    args = (int(k), int(bool(canonical)), int(n), int(seed), _cmdline_json(cmdline))
+    check(lib.km_jf_header(*args, None, 0, C.byref(ln), ptr(columns), C.byref(s)))
+    out = np.zeros(ln.value, np.uint8)
+    check(lib.km_jf_header(*args, ptr(out), out.size, C.byref(ln), ptr(columns), C.byref(s)))
+    return out.tobytes(), columns[:2 * int(k)].copy(), int(s.value)
+
+
+def jf_sort_records(columns, k, size_log2, keys, counts, device=0, want_pos=False):
+    """km_jf_sort_records: the file records (uint8[n, ceil(2k/8) + 4]) of (keys, counts) in (pos, key) order under
+    the matrix `columns` (2k words, r = size_log2 rows), sorted on the GPU; with want_pos also their positions."""
+    columns = np.ascontiguousarray(columns, dtype=np.uint64)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if keys.shape != counts.shape or keys.ndim != 1:
+        raise ValueError("keys and counts must be 1-d arrays of one length")
+    if 2 <= int(k) <= 32 and columns.size != 2 * int(k):
+        raise ValueError("%d columns for k=%d" % (columns.size, k))
+    rec = (2 * int(k) + 7) // 8 + 4
+    out = np.zeros((keys.size, rec), np.uint8)
+    pos = np.zeros(keys.size, np.uint64) if want_pos else None
+    check(load().km_jf_sort_records(int(device), ptr(columns), int(k), int(size_log2), ptr(keys), ptr(counts),
+                                    keys.size, ptr(out), ptr(pos), None))
+    return (out, pos) if want_pos else out
+
+
+def jf_sort_stats():
+    """km_jf_sort_stats of this thread's last sort: dict(buckets, largest, oversized, kernel_ms)."""
+    v = np.zeros(4, np.uint64)
+    ms = C.c_float()
+    check(load().km_jf_sort_stats(ptr(v)))
+    check(load().km_jf_sort_kernel_ms(C.byref(ms)))
+    return {"buckets": int(v[0]), "largest": int(v[1]), "oversized": int(v[2]), "kernel_ms": float(ms.value)}
 
 
 class Batch:

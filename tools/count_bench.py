@@ -9,19 +9,26 @@ timed as wall time around calls that end in km_counter_stats (which waits for th
                that stands for (8-byte key read + 4-byte add per k-mer, 8-byte compare-and-swap per new key)
   add_text   - the same reads as FASTQ text in 8 MB blocks, table grown from the default: bytes/s, n_grow
   finish     - compaction + lookup-table build, seconds
+  write_jf   - the kept records as a file in Jellyfish's own record order (Counter.write_jf: sorted on the device,
+               drained through pinned staging), wall seconds, best and all of --write-reps runs; the time of its
+               kernels alone (position, scan, scatter, sort; HIP events inside the call) and the bucket figures;
+               and beside them the path it replaces for a key-sorted file: Counter.records() + write_records,
+               which sorts with np.argsort (host_sorted_*).  Files go to /dev/shm if there is one, else to the temp directory.
 and km_device_copy_GBs of the same run for scale.
 
-usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31]
+usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31] [--write-reps 3]
 """
 import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from km_amd import count as kc  # noqa: E402
 from km_amd import lib as kmlib  # noqa: E402
 
 ACGT = np.frombuffer(b"ACGT", np.uint8)
@@ -64,7 +71,42 @@ def as_fastq(reads):
     return rows.reshape(-1)
 
 
-def run_size(name, k, device, rng):
+def time_writers(counter, k, reps):
+    """The field group of the two file writers on a finished counter."""
+    tmp = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else tempfile.gettempdir()
+    path = os.path.join(tmp, "count_bench_%d.jf" % os.getpid())
+    native, kernels, host, parts = [], [], [], None
+    try:
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            counter.write_jf(path)
+            native.append(time.perf_counter() - t0)
+            stats = kmlib.jf_sort_stats()
+            kernels.append(stats["kernel_ms"])
+            size = os.path.getsize(path)
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            keys, counts = counter.records()
+            t1 = time.perf_counter()
+            kc.write_records(path, keys, counts, k, counter.canonical)      # (its np.argsort included)
+            t2 = time.perf_counter()
+            host.append(t2 - t0)
+            if parts is None or host[-1] <= min(host):
+                parts = {"records_s": t1 - t0, "write_records_s": t2 - t1}
+    finally:
+        if os.path.exists(path):
+            os.unlink(path)
+    return {
+        "write_reps": reps, "write_dir": tmp, "write_jf_file_bytes": size,
+        "write_jf_s": min(native), "write_jf_s_all": native,
+        "write_jf_kernel_ms": min(kernels), "write_jf_kernel_ms_all": kernels,
+        "write_jf_buckets": stats["buckets"], "write_jf_largest_bucket": stats["largest"],
+        "write_jf_oversized_buckets": stats["oversized"],
+        "host_sorted_s": min(host), "host_sorted_s_all": host, "host_sorted_parts": parts,
+    }
+
+
+def run_size(name, k, device, rng, write_reps=3):
     genome_len, n_reads, stage = SIZES[name]
     if stage:
         os.environ["KM_COUNT_STAGE_BYTES"] = str(stage)
@@ -87,6 +129,7 @@ def run_size(name, k, device, rng):
     t_finish = time.perf_counter() - t0
     n_kept = int(db.info.n_records)
     db.close()
+    writers = time_writers(sized, k, write_reps)
     sized.close()
 
     grown = kmlib.Counter(k=k, device=device)
@@ -116,6 +159,7 @@ def run_size(name, k, device, rng):
         "add_text_s": t_text, "add_text_bytes_per_s": text.size / t_text, "add_text_kmers_per_s": st["kmers"] / t_text,
         "add_text_n_grow": st_text["n_grow"], "add_text_table_slots": st_text["slots"],
         "finish_s": t_finish,
+        **writers,
     }
 
 
@@ -124,12 +168,13 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--sizes", default="cache,hbm")
     ap.add_argument("-k", type=int, default=31)
+    ap.add_argument("--write-reps", type=int, default=3)
     args = ap.parse_args()
     kmlib.load()
     rng = np.random.default_rng(2026)
     out = {"tool": "count_bench", "k": args.k, "sizes": {}}
     for name in args.sizes.split(","):
-        out["sizes"][name] = run_size(name, args.k, args.device, rng)
+        out["sizes"][name] = run_size(name, args.k, args.device, rng, args.write_reps)
     out["km_device_copy_GBs"] = kmlib.device_copy_GBs(args.device, 1 << 30, 10)
     print(json.dumps(out))
 

@@ -390,6 +390,32 @@ int km_counter_add_bases(km_counter_t* c, const uint8_t* bytes, uint64_t n);
  * neither, a FASTQ record that does not start with '@' or lacks its '+' line; km_last_error names the byte
  * offset within the stream. */
 int km_counter_add_text(km_counter_t* c, const char* text, uint64_t n, int final, uint64_t* consumed);
+/* 4-line FASTQ text as it is, parsed on the GPU, with the quality masking of `jellyfish count -Q CHAR`
+ * (--min-qual-char; km's own counting command, example/run_leucegene.sh:22, passes '-Q+'): a base whose quality
+ * byte is below min_qual_char is read as N.  The comparison is strict and on the raw byte (no Phred offset), which
+ * is this project's reading of Jellyfish 2's option, not checked against a run of it; 0 masks nothing and then
+ * counts what km_counter_add_text counts.  The text is strict: line 4r starts with '@', line 4r+2 with '+', line
+ * 4r+3 is as long as line 4r+1 (a '\r' before the newline is dropped from both first), and — unlike
+ * km_counter_add_text — no blank lines between or behind records.  Whole records are taken, up to km_fastq_cut
+ * of the text; *consumed says how much, and the caller passes the rest again in front of the next block; with
+ * final != 0 everything is taken and the last line needs no newline.  The text goes to the device in pieces of
+ * whole records (no k-mer spans two pieces, or a change between this call and add_bases / add_text), where kernels
+ * find the lines, pair every base with its quality byte and hand a stream of bases and breaks to the insert kernel.
+ * KM_E_ARG for min_qual_char outside 0..255; KM_E_CAPACITY, naming the offset, for a record longer than a staging
+ * buffer (16 MiB).  A malformed record is found ASYNCHRONOUSLY, by the device: KM_E_FORMAT comes from the next
+ * call on this counter that waits for the device (a later add_* that has to grow the table, km_counter_stats,
+ * km_counter_finish), km_last_error names the kind and the smallest offending byte offset within the stream (all
+ * calls since the last final one), and every further call on the counter returns KM_E_FORMAT too. */
+int km_counter_add_fastq(km_counter_t* c, const char* text, uint64_t n, int final, int min_qual_char,
+                         uint64_t* consumed);
+/* Host only.  *cut = the largest offset <= n at which a record of 4-line FASTQ text ends: one past the newline of
+ * a quality line whose record is all there, 0 if no record is complete.  A header is told from a quality line that
+ * starts with '@' by the line two below it, which starts with '+' only below a header.  Found by walking back from
+ * the end over a handful of lines, not by a pass over the text. */
+int km_fastq_cut(const char* text, uint64_t n, uint64_t* cut);
+/* With KM_COUNT_TIME_FASTQ=1 in the environment of the first km_counter_add_fastq call: the time of the line-table
+ * and mask kernels of all pieces so far, by HIP events on the counter's stream (waits for it); 0 otherwise. */
+int km_counter_fastq_kernel_ms(km_counter_t* c, float* ms);
 /* waits for everything added so far */
 int km_counter_stats(km_counter_t* c, km_counter_stats_t* s);
 /* compacts (count >= lower_count), builds the lookup table on the counter's device through the same path

@@ -293,14 +293,18 @@ def main_count(args, err=None):
     """`jellyfish count -m K [-C] -L N -s SIZE -o OUT reads..` on the GPU (km_amd.count): the k-mers of the read
     files counted on the device, the records with count >= -L written to OUT (read by every tool here).  The file
     is sorted by key, which real Jellyfish could not query (km_amd.count.write_records); with --jellyfish-order
-    it is sorted on the device into Jellyfish's own record order and written from there (Counter.write_jf)."""
+    it is sorted on the device into Jellyfish's own record order and written from there (Counter.write_jf).
+    -Q CHAR (Jellyfish's --min-qual-char, as in example/run_leucegene.sh:22): FASTQ files are parsed on the GPU and
+    a base whose quality character is below CHAR is read as N (Counter.add_fastq)."""
     err = sys.stderr if err is None else err
     from . import count as kc
     db, stats, counter = kc.count_files(args.reads, k=args.mer_len, canonical=args.canonical,
                                         lower_count=args.lower_count, device=default_device(),
-                                        expected_distinct=args.size, keep_counter=True)
+                                        expected_distinct=args.size, keep_counter=True,
+                                        min_qual_char=args.min_qual_char)
     cmdline = ["km_amd", "count", "-m", str(args.mer_len)] + (["-C"] if args.canonical else []) + [
         "-L", str(args.lower_count), "-s", str(args.size)] + (
+        ["-Q", args.min_qual_char] if args.min_qual_char is not None else []) + (
         ["--jellyfish-order"] if args.jellyfish_order else []) + ["-o", args.output] + list(args.reads)
     try:
         if args.jellyfish_order:
@@ -312,11 +316,20 @@ def main_count(args, err=None):
         db.close()
     for key in ("bases", "kmers", "distinct", "slots", "n_grow"):
         err.write("#%s:%d\n" % (key, stats[key]))
+    if args.min_qual_char is not None:
+        err.write("#min_qual_char:%s\n" % args.min_qual_char)
     if not args.jellyfish_order:
         kc.write_records(args.output, keys, counts, args.mer_len, args.canonical, cmdline=cmdline)
 
 
-def main(argv=None):
+def _one_char(text):
+    """argparse type of -Q: exactly one character that is one byte."""
+    if len(text) != 1 or ord(text) > 255:
+        raise argparse.ArgumentTypeError("expected exactly one character, got %r" % text)
+    return text
+
+
+def build_parser():
     parser = argparse.ArgumentParser(prog="km")
     sub = parser.add_subparsers(dest="_cmd")
     fm = sub.add_parser("find_mutation")
@@ -344,7 +357,15 @@ def main(argv=None):
     ct.add_argument("-o", "--output", default="mer_counts.jf", help="output file (default: mer_counts.jf)")
     ct.add_argument("--jellyfish-order", action="store_true",
                     help="write the records in Jellyfish's own order (matrix position, then key), sorted on the GPU")
+    ct.add_argument("-Q", "--min-qual-char", type=_one_char, default=None, metavar="CHAR",
+                    help="a base of a FASTQ read whose quality character is below CHAR is read as N (FASTQ is then "
+                         "parsed on the GPU; no effect on FASTA)")
     ct.add_argument("reads", nargs="+", help="FASTA or FASTQ files, plain or gzip; - is stdin")
+    return parser
+
+
+def main(argv=None):
+    parser = build_parser()
     args = parser.parse_args(argv)
     cmd = args._cmd
     del args._cmd

@@ -30,34 +30,49 @@ def _open(path):
     return fh, True
 
 
-def feed_file(counter, path, block=BLOCK):
-    """One file through counter.add_text in blocks, the unconsumed tail carried in front of the next block."""
+def feed_file(counter, path, block=BLOCK, min_qual_char=None):
+    """One file through counter.add_text in blocks, the unconsumed tail carried in front of the next block.
+    With min_qual_char (not None) a file whose first non-blank byte is '@' goes through counter.add_fastq with
+    that quality threshold instead, from that byte on; a FASTA file has no qualities and takes add_text."""
     fh, close = _open(path)
     try:
         tail = b""
+        add = None if min_qual_char is not None else counter.add_text
         while True:
             data = fh.read(block)
             if not data:
                 break
             buf = tail + data if tail else data
-            used = counter.add_text(buf, final=False)
+            if add is None:
+                buf = buf.lstrip(b"\r\n")
+                if not buf:
+                    continue
+                if buf[:1] == b"@":
+                    def add(text, final, _q=min_qual_char):
+                        return counter.add_fastq(text, final=final, min_qual_char=_q)
+                else:
+                    add = counter.add_text
+            used = add(buf, final=False)
             tail = buf[used:]
-        counter.add_text(tail, final=True)
+        (add or counter.add_text)(tail, final=True)
     finally:
         if close:
             fh.close()
 
 
-def count_files(paths, k=31, canonical=True, lower_count=1, device=0, expected_distinct=0, keep_counter=False):
+def count_files(paths, k=31, canonical=True, lower_count=1, device=0, expected_distinct=0, keep_counter=False,
+                min_qual_char=None):
     """Count the k-mers of every read of `paths` (FASTA or 4-line FASTQ, gzip recognised by its magic, '-' =
     stdin) -> (Database, stats).  stats is the dict of Counter.stats() before the cut at lower_count.
-    keep_counter=True returns (Database, stats, Counter) so that the caller can fetch the records."""
+    keep_counter=True returns (Database, stats, Counter) so that the caller can fetch the records.
+    min_qual_char (an int or one character; Jellyfish's -Q): FASTQ files are parsed on the GPU (Counter.add_fastq)
+    and a base whose quality byte is below it is read as N; None: the host stripper, qualities never looked at."""
     if isinstance(paths, (str, bytes)):
         paths = [paths]
     counter = _lib.Counter(k=k, canonical=canonical, device=device, expected_distinct=expected_distinct)
     try:
         for p in paths:
-            feed_file(counter, p)
+            feed_file(counter, p, min_qual_char=min_qual_char)
         stats = counter.stats()
         db = counter.finish(lower_count)
     except BaseException:

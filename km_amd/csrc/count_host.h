@@ -1,14 +1,38 @@
-// count_host.h — km_counter_*, km_text_strip (host part of kmgpu.hip; device side: count_kernel.h, fastx_strip.h)
+// count_host.h — km_counter_*, km_text_strip, km_fastq_cut (host part of kmgpu.hip; device side: count_kernel.h,
+// fastq_kernel.h; host helpers: fastx_strip.h, fastq_cut.h)
 // ------------------------------------------------------------------ counting k-mers from reads
 // km_counter (include/kmgpu.h): text or bases are staged in two pinned buffers that take turns,
 // copied and inserted (count_kernel.h) on the counter's own stream, so the host strips the next block while the
 // device inserts the last.  What is staged is ONE byte stream (bases and breaks); it is cut into pieces of the
 // staging size that overlap by exactly k - 1 bytes, and a piece counts the windows that lie wholly inside it:
 // piece i covers [i (S - k + 1), i (S - k + 1) + S), so a window of k bytes lies wholly inside exactly one piece.
+// km_counter_add_fastq stages raw FASTQ text instead, in pieces of whole records that overlap by nothing, and the
+// device turns each piece into such a byte stream of its own (fastq_kernel.h) in front of the same insert kernel.
 namespace {
 constexpr uint64_t COUNT_STAGE_BYTES = 16ull << 20;     // per pinned buffer (KM_COUNT_STAGE_BYTES: tests)
 constexpr uint64_t COUNT_DEFAULT_SLOTS = 1ull << 16;
 uint64_t key_space(int k) { return k >= 32 ? ~0ull : (1ull << (2 * k)); }
+
+// What km_counter_add_fastq needs on the device beside d_text, allocated by its first call.
+struct FastqDev {
+  DevBuf<uint8_t> masked;                 // the piece as k_count_insert reads it (k_fq_mask's output)
+  DevBuf<uint32_t> tiles, sums;           // newlines per tile, scanned in place (k_scan_*), and the chunk sums
+  DevBuf<uint32_t> line_start;
+  bool timed = false;                     // KM_COUNT_TIME_FASTQ: an event pair around every piece's kernels
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> spans;
+  float kernel_ms = 0.f;
+  ~FastqDev() { for (auto& s : spans) { (void)hipEventDestroy(s.first); (void)hipEventDestroy(s.second); } }
+};
+
+const char* fastq_error_text(unsigned kind) {
+  switch (kind) {
+    case FQ_NO_AT: return "FASTQ record does not start with '@'";
+    case FQ_NO_PLUS: return "FASTQ record lacks its '+' line";
+    case FQ_QUAL_LEN: return "FASTQ quality line is not as long as its sequence";
+    case FQ_TRUNCATED: return "FASTQ record is incomplete";
+  }
+  return "FASTQ text is malformed";
+}
 }  // namespace
 
 struct km_counter {
@@ -28,6 +52,9 @@ struct km_counter {
   uint32_t n_grow = 0;
   bool finished = false;
   km_text_state_t text = {0, 0, 0, 0, 0};
+  std::unique_ptr<FastqDev> fq;           // (after st: its events go before the stream)
+  uint64_t fq_offset = 0;                 // bytes km_counter_add_fastq consumed in the earlier calls of this stream
+  unsigned long long fq_error = FQ_NO_ERROR;   // what the device found, once read: (stream offset << 8) | kind
   km_counter_stats_t last = {0, 0, 0, 0, 0, 0};
   DevBuf<uint64_t> out_keys;
   DevBuf<uint32_t> out_counts;
@@ -38,11 +65,21 @@ struct km_counter {
   }
 };
 
+// A format error the device found (km_counter_add_fastq) stays with the counter: every call from then on fails.
+static int counter_format_failed(const km_counter* c) {
+  return fail(KM_E_FORMAT, "%s at byte offset %llu", fastq_error_text((unsigned)(c->fq_error & 0xFF)),
+              (unsigned long long)(c->fq_error >> 8));
+}
+
 // waits for everything enqueued
 static int counter_read_meta(km_counter* c, unsigned long long* m) {
   HIPCHK(hipMemcpyAsync(m, c->meta, CM_WORDS * 8, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   if (m[CM_ERROR]) return fail(KM_E_HIP, "counting table ran full (%llu keys not placed)", m[CM_ERROR]);
+  if (m[CM_FORMAT] != FQ_NO_ERROR) {
+    c->fq_error = m[CM_FORMAT];
+    return counter_format_failed(c);
+  }
   c->last.bases = m[CM_BASES];
   c->last.kmers = m[CM_KMERS];
   c->last.distinct = m[CM_DISTINCT] + (m[CM_ALLT] ? 1 : 0);
@@ -149,6 +186,7 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
     HIPCHK(hipEventCreateWithFlags(&c->copied[i].h, hipEventDisableTiming));
   }
   HIPCHK(hipMemsetAsync(c->meta, 0, CM_WORDS * 8, c->st));
+  HIPCHK(hipMemsetAsync(c->meta.p + CM_FORMAT, 0xFF, 8, c->st));        // FQ_NO_ERROR
   hipLaunchKernelGGL(k_count_init, dim3(grid_for(c->slots, 256)), dim3(256), 0, c->st, c->table.p, c->slots);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->st));
@@ -160,6 +198,7 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
 extern "C" int km_counter_add_bases(km_counter_t* c, const uint8_t* bytes, uint64_t n) {
   if (!c || (n && !bytes)) return fail(KM_E_ARG, "null argument");
   if (c->finished) return fail(KM_E_STATE, "counter already finished");
+  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
   if (n == 0) return KM_OK;
   HIPCHK(hipSetDevice(c->device));
   int rc = counter_append(c, bytes, n);
@@ -189,6 +228,7 @@ int strip_failed(const kmstrip::Result& r) {
 extern "C" int km_counter_add_text(km_counter_t* c, const char* text, uint64_t n, int final, uint64_t* consumed) {
   if (!c || !consumed || (n && !text)) return fail(KM_E_ARG, "null argument");
   if (c->finished) return fail(KM_E_STATE, "counter already finished");
+  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
   *consumed = 0;
   if (n == 0 && !final) return KM_OK;
   HIPCHK(hipSetDevice(c->device));
@@ -197,6 +237,120 @@ extern "C" int km_counter_add_text(km_counter_t* c, const char* text, uint64_t n
   *consumed = r.consumed;
   if (sink.rc != KM_OK) return sink.rc;
   if (r.error) return strip_failed(r);
+  return KM_OK;
+}
+
+// ---- raw FASTQ text, parsed on the device
+static int fastq_prepare(km_counter* c) {
+  if (c->fq) return KM_OK;
+  if (c->stage >= 0xFFFFFFF0ull) return fail(KM_E_ARG, "staging buffers of %llu bytes: the line table is 32-bit",
+                                             (unsigned long long)c->stage);
+  std::unique_ptr<FastqDev> f(new (std::nothrow) FastqDev);
+  if (!f) return fail(KM_E_NOMEM, "host allocation failed");
+  const uint64_t max_tiles = (c->stage + FQ_TILE - 1) / FQ_TILE;
+  const uint64_t max_chunks = (max_tiles + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK;
+  KMCHK(f->masked.alloc(c->stage + COUNT_PAD));
+  KMCHK(f->tiles.alloc(max_chunks * SCAN_CHUNK));
+  KMCHK(f->sums.alloc(max_chunks));
+  KMCHK(f->line_start.alloc(c->stage + 2));           // a piece of n bytes has at most n newlines
+  if (const char* e = getenv("KM_COUNT_TIME_FASTQ")) f->timed = atoi(e) != 0;
+  c->fq = std::move(f);
+  return KM_OK;
+}
+
+// One piece of whole records, text[0 .. n) with n <= stage: copy -> line table -> mask -> insert, all on the
+// counter's stream.  base: the piece's offset in the stream (for what the validation reports).
+static int fastq_enqueue(km_counter* c, const char* text, uint64_t n, uint64_t base, uint32_t min_qual) {
+  FastqDev& f = *c->fq;
+  HIPCHK(hipEventSynchronize(c->copied[c->cur]));
+  memcpy(c->pin[c->cur], text, n);
+  KMCHK(counter_reserve(c, n));                         // every byte taken as a window: a bound, and a loose one
+  HIPCHK(hipMemcpyAsync(c->d_text, c->pin[c->cur], n, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipEventRecord(c->copied[c->cur], c->st));
+  c->cur ^= 1;
+  const uint32_t n_tiles = (uint32_t)((n + FQ_TILE - 1) / FQ_TILE);
+  const uint32_t n_chunks = (uint32_t)(((uint64_t)n_tiles + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK);
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  if (f.timed) {
+    HIPCHK(hipEventCreate(&t0));
+    hipError_t e = hipEventCreate(&t1);
+    if (e != hipSuccess) { (void)hipEventDestroy(t0); return fail_hip(KM_E_HIP, "hipEventCreate", e); }
+    f.spans.emplace_back(t0, t1);
+    HIPCHK(hipEventRecord(t0, c->st));
+  }
+  HIPCHK(hipMemsetAsync(f.tiles, 0, (uint64_t)n_chunks * SCAN_CHUNK * 4, c->st));
+  hipLaunchKernelGGL(k_fq_count_lines, dim3(n_tiles), dim3(FQ_THREADS), 0, c->st, c->d_text.p, n, f.tiles.p);
+  hipLaunchKernelGGL(k_scan_reduce, dim3(n_chunks), dim3(SCAN_THREADS), 0, c->st, f.tiles.p, f.sums.p);
+  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, c->st, f.sums.p, n_chunks);
+  hipLaunchKernelGGL(k_scan_apply, dim3(n_chunks), dim3(SCAN_THREADS), 0, c->st, f.tiles.p, f.sums.p);
+  hipLaunchKernelGGL(k_fq_line_starts, dim3(n_tiles), dim3(FQ_THREADS), 0, c->st, c->d_text.p, n, f.tiles.p, n_tiles,
+                     f.line_start.p);
+  hipLaunchKernelGGL(k_fq_mask, dim3(n_tiles), dim3(FQ_THREADS), 0, c->st, c->d_text.p, n, f.tiles.p, n_tiles,
+                     f.line_start.p, min_qual, base, f.masked.p, c->meta.p + CM_FORMAT);
+  HIPCHK(hipGetLastError());
+  if (f.timed) HIPCHK(hipEventRecord(t1, c->st));
+  const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
+  hipLaunchKernelGGL(k_count_insert, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, c->st, f.masked.p, n, 0u,
+                     c->k, c->canonical, c->table.p, c->slots - 1, c->meta.p);
+  HIPCHK(hipGetLastError());
+  return KM_OK;
+}
+
+extern "C" int km_fastq_cut(const char* text, uint64_t n, uint64_t* cut) {
+  if (!cut || (n && !text)) return fail(KM_E_ARG, "null argument");
+  *cut = kmcut::cut(text, n);
+  return KM_OK;
+}
+
+extern "C" int km_counter_add_fastq(km_counter_t* c, const char* text, uint64_t n, int final, int min_qual_char,
+                                    uint64_t* consumed) {
+  if (!c || !consumed || (n && !text)) return fail(KM_E_ARG, "null argument");
+  if (min_qual_char < 0 || min_qual_char > 255) return fail(KM_E_ARG, "min_qual_char %d outside 0..255", min_qual_char);
+  if (c->finished) return fail(KM_E_STATE, "counter already finished");
+  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
+  *consumed = 0;
+  const uint64_t end = final ? n : kmcut::cut(text, n);
+  if (end) {
+    HIPCHK(hipSetDevice(c->device));
+    KMCHK(fastq_prepare(c));
+    // what add_bases / add_text left goes first; the bytes it would carry over are dropped: no k-mer spans a
+    // change between the two kinds of calls
+    KMCHK(counter_flush(c));
+    c->fill = 0;
+    c->own_from = 0;
+  }
+  for (uint64_t pos = 0; pos < end;) {
+    uint64_t take = end - pos;
+    if (take > c->stage) {
+      take = kmcut::cut(text + pos, c->stage);
+      if (take == 0)
+        return fail(KM_E_CAPACITY, "no FASTQ record ends within the %llu bytes of a staging buffer from byte offset %llu",
+                    (unsigned long long)c->stage, (unsigned long long)(c->fq_offset + pos));
+    }
+    KMCHK(fastq_enqueue(c, text + pos, take, c->fq_offset + pos, (uint32_t)min_qual_char));
+    pos += take;
+    *consumed = pos;
+  }
+  if (end) HIPCHK(hipEventSynchronize(c->copied[c->cur]));     // add_bases / add_text write pin[cur] without asking
+  c->fq_offset = final ? 0 : c->fq_offset + end;
+  return KM_OK;
+}
+
+extern "C" int km_counter_fastq_kernel_ms(km_counter_t* c, float* ms) {
+  if (!c || !ms) return fail(KM_E_ARG, "null argument");
+  *ms = 0.f;
+  if (!c->fq) return KM_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->st));
+  for (auto& s : c->fq->spans) {
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, s.first, s.second));
+    c->fq->kernel_ms += t;
+    (void)hipEventDestroy(s.first);
+    (void)hipEventDestroy(s.second);
+  }
+  c->fq->spans.clear();
+  *ms = c->fq->kernel_ms;
   return KM_OK;
 }
 
@@ -216,6 +370,7 @@ extern "C" int km_text_strip(km_text_state_t* st, const char* text, uint64_t n, 
 
 extern "C" int km_counter_stats(km_counter_t* c, km_counter_stats_t* s) {
   if (!c || !s) return fail(KM_E_ARG, "null argument");
+  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
   if (!c->finished) {
     HIPCHK(hipSetDevice(c->device));
     int rc = counter_flush(c);
@@ -230,6 +385,7 @@ extern "C" int km_counter_stats(km_counter_t* c, km_counter_stats_t* s) {
 extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t** out) {
   if (!c || !out) return fail(KM_E_ARG, "null argument");
   if (c->finished) return fail(KM_E_STATE, "counter already finished");
+  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
   HIPCHK(hipSetDevice(c->device));
   int rc = counter_flush(c);
   unsigned long long m[CM_WORDS];
@@ -261,6 +417,7 @@ extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t**
   c->n_out = n;
   c->table.release();
   c->d_text.release();
+  if (c->fq) { c->fq->masked.release(); c->fq->tiles.release(); c->fq->sums.release(); c->fq->line_start.release(); }
   c->finished = true;
   *out = h;
   return KM_OK;

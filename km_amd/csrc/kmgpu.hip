@@ -6,7 +6,7 @@
 //   batch_host.h   knobs, km_batch (what a batch owns), set_targets, one step: km_batch_run, km_batch_sync
 //   result_host.h  reading a delivered step: km_batch_result / _pump / _fetch, diagnostics and measurement exports
 //   kmin_host.h    km_linear_kmin
-//   count_host.h   km_counter_*, km_text_strip
+//   count_host.h   km_counter_*, km_text_strip, km_fastq_cut
 //   jf_order_host.h  km_jf_*, km_counter_write_jf: files in Jellyfish's own record order
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
@@ -32,6 +32,8 @@
 #include "count_kernel.h"
 #include "deliver_kernel.h"
 #include "device_common.h"
+#include "fastq_cut.h"
+#include "fastq_kernel.h"
 #include "fastx_strip.h"
 #include "graph_kernel.h"
 #include "jf_order_kernel.h"

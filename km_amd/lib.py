@@ -37,6 +37,7 @@ SYMBOLS = [
     "km_report_rows", "km_report_free", "km_linear_kmin", "km_strerror", "km_last_error",
     "km_counter_create", "km_counter_add_bases", "km_counter_add_text", "km_counter_stats", "km_counter_finish",
     "km_counter_records", "km_counter_destroy", "km_text_strip",
+    "km_counter_add_fastq", "km_fastq_cut", "km_counter_fastq_kernel_ms",
     "km_jf_matrix", "km_jf_sort_records", "km_jf_sort_stats", "km_jf_sort_kernel_ms", "km_jf_header",
     "km_counter_write_jf",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
@@ -224,6 +225,9 @@ def load():
         "km_counter_create": [i32, i32, i32, u64, C.POINTER(vp)],
         "km_counter_add_bases": [vp, vp, u64],
         "km_counter_add_text": [vp, vp, u64, i32, C.POINTER(u64)],
+        "km_counter_add_fastq": [vp, vp, u64, i32, i32, C.POINTER(u64)],
+        "km_fastq_cut": [vp, u64, C.POINTER(u64)],
+        "km_counter_fastq_kernel_ms": [vp, C.POINTER(C.c_float)],
         "km_counter_stats": [vp, C.POINTER(CounterStats)],
         "km_counter_finish": [vp, u32, C.POINTER(vp)],
         "km_counter_records": [vp, vp, vp, u64, C.POINTER(u64)],
@@ -450,9 +454,29 @@ def strip_text(text, final=True, state=None):
     return out[:n_out.value].tobytes(), int(consumed.value), st
 
 
+def fastq_cut(data):
+    """km_fastq_cut: the largest offset at which a record of the 4-line FASTQ text `data` ends (0: no complete
+    record).  Host only."""
+    buf = _byte_view(data)
+    cut = C.c_uint64()
+    check(load().km_fastq_cut(ptr(buf) if buf.size else None, buf.size, C.byref(cut)))
+    return int(cut.value)
+
+
+def _qual_byte(min_qual_char):
+    """0..255 from an int, or from a str / bytes of one character."""
+    if isinstance(min_qual_char, str):
+        min_qual_char = min_qual_char.encode("latin-1")
+    if isinstance(min_qual_char, (bytes, bytearray)):
+        if len(min_qual_char) != 1:
+            raise ValueError("min_qual_char must be one character")
+        return min_qual_char[0]
+    return int(min_qual_char)
+
+
 class Counter:
     """k-mers counted from reads on the GPU (km_counter_*, include/kmgpu.h): what `jellyfish count -m k [-C]
-    -s expected_distinct` does.  add_bases / add_text feed it, finish() hands back a Database whose table was
+    -s expected_distinct` does.  add_bases / add_text / add_fastq feed it, finish() hands back a Database whose table was
     built on the device from the counted records."""
 
     def __init__(self, k=31, canonical=True, device=0, expected_distinct=0):
@@ -487,6 +511,23 @@ class Counter:
         check(self._lib.km_counter_add_text(self._c, ptr(buf) if buf.size else None, buf.size, int(bool(final)),
                                             C.byref(consumed)))
         return int(consumed.value)
+
+    def add_fastq(self, data, final=False, min_qual_char=0):
+        """4-line FASTQ text, parsed on the GPU; a base whose quality byte is below min_qual_char (an int, or one
+        character; 0 masks nothing) is read as N, as by `jellyfish count -Q`.  Returns how many bytes were taken
+        (whole records): pass the rest again in front of the next block.  A malformed record raises KmError
+        (KM_E_FORMAT) from a LATER call that waits for the device: stats(), finish()."""
+        buf = _byte_view(data)
+        consumed = C.c_uint64()
+        check(self._lib.km_counter_add_fastq(self._c, ptr(buf) if buf.size else None, buf.size, int(bool(final)),
+                                             _qual_byte(min_qual_char), C.byref(consumed)))
+        return int(consumed.value)
+
+    def fastq_kernel_ms(self):
+        """km_counter_fastq_kernel_ms: time of add_fastq's own kernels so far (needs KM_COUNT_TIME_FASTQ=1)."""
+        ms = C.c_float()
+        check(self._lib.km_counter_fastq_kernel_ms(self._c, C.byref(ms)))
+        return float(ms.value)
 
     def stats(self):
         """dict of km_counter_stats_t (waits for everything added so far)."""

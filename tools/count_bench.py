@@ -8,6 +8,12 @@ timed as wall time around calls that end in km_counter_stats (which waits for th
   add_bases  - pre-stripped bytes, table sized in advance (expected_distinct): k-mers/s, and the table traffic
                that stands for (8-byte key read + 4-byte add per k-mer, 8-byte compare-and-swap per new key)
   add_text   - the same reads as FASTQ text in 8 MB blocks, table grown from the default: bytes/s, n_grow
+  add_fastq  - the same FASTQ text in the same blocks through Counter.add_fastq (lines, qualities and the mask on
+               the device), with Q = 0 and with Q = '+': wall time, text bytes/s, k-mers/s, and the time of the
+               line-table and mask kernels by HIP events on the counter's stream (KM_COUNT_TIME_FASTQ).  The
+               qualities are seeded bytes in '!'..'I', 2 % of them below '+'.  add_text and the two add_fastq runs
+               alternate --text-reps times within the run; best and all times are reported, the base of any
+               comparison is add_text of the same run
   finish     - compaction + lookup-table build, seconds
   write_jf   - the kept records as a file in Jellyfish's own record order (Counter.write_jf: sorted on the device,
                drained through pinned staging), wall seconds, best and all of --write-reps runs; the time of its
@@ -16,7 +22,7 @@ timed as wall time around calls that end in km_counter_stats (which waits for th
                which sorts with np.argsort (host_sorted_*).  Files go to /dev/shm if there is one, else to the temp directory.
 and km_device_copy_GBs of the same run for scale.
 
-usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31] [--write-reps 3]
+usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31] [--write-reps 3] [--text-reps 3]
 """
 import argparse
 import json
@@ -60,15 +66,68 @@ def as_stream(reads):
     return rows.reshape(-1)
 
 
-def as_fastq(reads):
+def as_fastq(reads, rng):
     n, ln = reads.shape
     rows = np.empty((n, 3 + ln + 3 + ln + 1), np.uint8)
     rows[:, :3] = np.frombuffer(b"@r\n", np.uint8)
     rows[:, 3:3 + ln] = reads
     rows[:, 3 + ln:6 + ln] = np.frombuffer(b"\n+\n", np.uint8)
-    rows[:, 6 + ln:6 + 2 * ln] = ord("I")
+    qual = rows[:, 6 + ln:6 + 2 * ln]
+    qual[:] = ord("I")
+    for lo in range(0, n, 200_000):
+        part = qual[lo:lo + 200_000]
+        low = rng.random(part.shape) < 0.02
+        part[low] = rng.integers(ord("!"), ord("+"), int(low.sum()))
     rows[:, -1] = ord("\n")
     return rows.reshape(-1)
+
+
+def feed_blocks(add, text, block=8 << 20):
+    pos, tail = 0, b""
+    while pos < text.size:
+        buf = text[pos:pos + block]
+        pos += block
+        if len(tail):
+            buf = np.concatenate([tail, buf])
+        used = add(buf, False)
+        tail = buf[used:]
+    add(tail, True)
+
+
+def time_text_paths(k, device, text, reps):
+    """add_text and add_fastq (Q = 0, Q = '+') on the same text, alternating, each on a counter of its own grown
+    from the default; wall time around calls that end in stats()."""
+    os.environ["KM_COUNT_TIME_FASTQ"] = "1"
+    paths = {"add_text": None, "add_fastq_q0": 0, "add_fastq_qplus": ord("+")}
+    wall = {name: [] for name in paths}
+    kernel_ms = {name: [] for name in paths if paths[name] is not None}
+    stats = {}
+    for _ in range(reps):
+        for name, q in paths.items():
+            c = kmlib.Counter(k=k, device=device)
+            if q is None:
+                add = lambda buf, final: c.add_text(buf, final=final)                         # noqa: E731
+            else:
+                add = lambda buf, final: c.add_fastq(buf, final=final, min_qual_char=q)       # noqa: E731
+            t0 = time.perf_counter()
+            feed_blocks(add, text)
+            stats[name] = c.stats()
+            wall[name].append(time.perf_counter() - t0)
+            if q is not None:
+                kernel_ms[name].append(c.fastq_kernel_ms())
+            c.finish(2).close()
+            c.close()
+    assert (stats["add_fastq_q0"]["kmers"], stats["add_fastq_q0"]["distinct"]) == (
+        stats["add_text"]["kmers"], stats["add_text"]["distinct"])
+    out = {"text_reps": reps, "text_bytes": int(text.size)}
+    for name in paths:
+        best = min(wall[name])
+        out.update({name + "_s": best, name + "_s_all": wall[name], name + "_bytes_per_s": text.size / best,
+                    name + "_kmers": stats[name]["kmers"], name + "_kmers_per_s": stats[name]["kmers"] / best,
+                    name + "_n_grow": stats[name]["n_grow"], name + "_table_slots": stats[name]["slots"]})
+        if name in kernel_ms:
+            out.update({name + "_kernel_ms": min(kernel_ms[name]), name + "_kernel_ms_all": kernel_ms[name]})
+    return out, stats["add_text"]
 
 
 def time_writers(counter, k, reps):
@@ -106,14 +165,14 @@ def time_writers(counter, k, reps):
     }
 
 
-def run_size(name, k, device, rng, write_reps=3):
+def run_size(name, k, device, rng, write_reps=3, text_reps=3):
     genome_len, n_reads, stage = SIZES[name]
     if stage:
         os.environ["KM_COUNT_STAGE_BYTES"] = str(stage)
     else:
         os.environ.pop("KM_COUNT_STAGE_BYTES", None)
     reads = make_reads(rng, genome_len, n_reads)
-    stream, text = as_stream(reads), as_fastq(reads)
+    stream, text = as_stream(reads), as_fastq(reads, rng)
     warm = kmlib.Counter(k=k, device=device)              # code object load, first allocations
     warm.add_bases(stream[:1_000_000])
     warm.finish().close()
@@ -132,23 +191,8 @@ def run_size(name, k, device, rng, write_reps=3):
     writers = time_writers(sized, k, write_reps)
     sized.close()
 
-    grown = kmlib.Counter(k=k, device=device)
-    block = 8 << 20
-    t0 = time.perf_counter()
-    pos, tail = 0, b""
-    while pos < text.size:
-        buf = text[pos:pos + block]
-        pos += block
-        if len(tail):
-            buf = np.concatenate([tail, buf])
-        used = grown.add_text(buf, final=False)
-        tail = buf[used:]
-    grown.add_text(tail, final=True)
-    st_text = grown.stats()
-    t_text = time.perf_counter() - t0
+    text_paths, st_text = time_text_paths(k, device, text, text_reps)
     assert (st_text["kmers"], st_text["distinct"]) == (st["kmers"], st["distinct"])
-    grown.finish(2).close()
-    grown.close()
     traffic = 12 * st["kmers"] + 8 * st["distinct"]
     return {
         "reads": n_reads, "bases": st["bases"], "kmers": st["kmers"], "distinct": st["distinct"],
@@ -156,8 +200,7 @@ def run_size(name, k, device, rng, write_reps=3):
         "staging_bytes": stage or 16 << 20,
         "add_bases_s": t_bases, "add_bases_kmers_per_s": st["kmers"] / t_bases, "add_bases_n_grow": st["n_grow"],
         "add_bases_table_GBs": traffic / t_bases / 1e9,
-        "add_text_s": t_text, "add_text_bytes_per_s": text.size / t_text, "add_text_kmers_per_s": st["kmers"] / t_text,
-        "add_text_n_grow": st_text["n_grow"], "add_text_table_slots": st_text["slots"],
+        **text_paths,
         "finish_s": t_finish,
         **writers,
     }
@@ -169,12 +212,13 @@ def main():
     ap.add_argument("--sizes", default="cache,hbm")
     ap.add_argument("-k", type=int, default=31)
     ap.add_argument("--write-reps", type=int, default=3)
+    ap.add_argument("--text-reps", type=int, default=3)
     args = ap.parse_args()
     kmlib.load()
     rng = np.random.default_rng(2026)
     out = {"tool": "count_bench", "k": args.k, "sizes": {}}
     for name in args.sizes.split(","):
-        out["sizes"][name] = run_size(name, args.k, args.device, rng, args.write_reps)
+        out["sizes"][name] = run_size(name, args.k, args.device, rng, args.write_reps, args.text_reps)
     out["km_device_copy_GBs"] = kmlib.device_copy_GBs(args.device, 1 << 30, 10)
     print(json.dumps(out))
 

@@ -62,9 +62,7 @@ CreateOptions read_create_options() {
 // ---------------------------------------------------------------------------- batch
 namespace {
 
-constexpr uint32_t FAST_EXTRA = 160;          // walk-discovered nodes a fast-tier target may add
-constexpr uint32_t FAST_LDS_LIMIT = 64 * 1024;
-constexpr uint32_t FAST_BCAP_MAX = 512;       // branch frames the fast tier keeps in LDS
+// (FAST_EXTRA, FAST_LDS_LIMIT, FAST_BCAP_MAX, what fits the fast tier, and round_up: tier_geometry.h)
 constexpr uint32_t FAST_FCAP_MAX = 4096;      // stack frames per target in the fast tier's scratch
 constexpr uint32_t LOOP_LOG_CAP = 4096;       // loop breaks of a batch kept for km_batch_graph_log (the rest is counted only)
 constexpr uint32_t BIG_DEV_SLOTS = 32;        // targets per run the device's own large tier takes (the rest: the host's)
@@ -637,37 +635,16 @@ static void fill_graph_args(km_batch* b, GraphArgs& g) {
 // branch-frame or stack-frame allowance) are flagged T_NEEDS_BIG by the kernels themselves, one
 // by one, and finished by the large tier in km_batch_sync.  One long target does not demote the
 // rest of its batch.
-static uint32_t words_cap_for(uint32_t len) { return round_up((len + 31) / 32 + 1, 2); }
-// slots of the graph kernels' node hash: load <= 2/3
-static uint32_t graph_hcap(uint32_t ncap) { return round_up(ncap + ncap / 2 + 1, 64); }
-
-// slots of k_dfs's node set in the fast tier.  It holds the walk's nodes, the stack, and the target k-mers that lost
-// their slot of the position table (a fifth of them with the table at load 1/2): room for a quarter of the target's
-// k-mers + every allowed extra node + 64 frames, at load <= 3/4 (what does not fit goes to the large tier)
-static uint32_t walk_hs_cap(uint32_t nref) { return round_up((uint32_t)(((uint64_t)(nref / 4 + FAST_EXTRA + 64) * 4 + 2) / 3), 64); }
-// slots of its position table: the power of two >= four times the target's k-mers (load <= 1/4: a tenth of the k-mers lose their slot)
-static uint32_t walk_pcap(uint32_t nref) { uint32_t p = 64; while (p < 4 * nref) p <<= 1; return p; }
-
-static bool fast_fits(const km_batch* b, uint32_t nref, uint32_t bcap) {
-  const uint32_t len = nref + (uint32_t)b->db->k - 1;
-  const uint32_t wc = words_cap_for(len);
-  const uint32_t hs = walk_hs_cap(nref);
-  const uint32_t ncap = nref + FAST_EXTRA + 2, hcap = graph_hcap(ncap);
-  return walk_lds_bytes(hs, wc, bcap, walk_pcap(nref), 2) <= FAST_LDS_LIMIT &&
-         graph_ws_bytes<uint16_t>(ncap, hcap, wc) <= FAST_LDS_LIMIT && ncap < 0xFFFF &&
-         (uint64_t)hcap * 4 + (uint64_t)wc * 8 <= FAST_LDS_LIMIT;   // (k_graph_pure hands over what its own table cannot hold)
-}
-
 static void fast_geometry(km_batch* b) {
   const int k = b->db->k;
   const uint32_t max_nref = b->max_len >= (uint32_t)k ? b->max_len - k + 1 : 1;
   const uint32_t bcap = std::min<uint32_t>(b->p.max_break, FAST_BCAP_MAX - 1) + 1;
   uint32_t nref = max_nref;
-  if (!fast_fits(b, nref, bcap)) {
+  if (!fast_tier_fits(k, nref, bcap)) {
     uint32_t lo = 1, hi = max_nref;          // fits(lo) holds: a 1-k-mer target always fits
     while (lo + 1 < hi) {
       const uint32_t mid = lo + (hi - lo) / 2;
-      if (fast_fits(b, mid, bcap)) lo = mid; else hi = mid;
+      if (fast_tier_fits(k, mid, bcap)) lo = mid; else hi = mid;
     }
     nref = lo;
   }

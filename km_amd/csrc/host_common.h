@@ -47,8 +47,6 @@ extern "C" int km_device_count(int* n) {
 
 static int fail_hip(int code, const char* what, hipError_t e) { return fail(code, "%s: %s", what, hipGetErrorString(e)); }
 
-static uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
-
 static int grid_for(uint64_t n, int block) {
   uint64_t g = (n + block - 1) / block;
   if (g < 1) g = 1;

@@ -3,6 +3,7 @@
 // One translation unit; the host code is in the parts included at the bottom, one per subsystem:
 //   host_common.h  error plumbing, owners of device memory / events / streams, the stream pool, km_stream_*
 //   db_host.h      the database: kmjf_* open / upload / broadcast / load, the lookups
+//   tier_geometry.h  what the LDS tier can hold (constants, fast_tier_fits)
 //   batch_host.h   knobs, km_batch (what a batch owns), set_targets, one step: km_batch_run, km_batch_sync
 //   result_host.h  reading a delivered step: km_batch_result / _pump / _fetch, diagnostics and measurement exports
 //   kmin_host.h    km_linear_kmin
@@ -46,6 +47,7 @@ using namespace kmd;
 
 #include "host_common.h"
 #include "db_host.h"
+#include "tier_geometry.h"
 #include "batch_host.h"
 #include "result_host.h"
 #include "kmin_host.h"

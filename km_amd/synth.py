@@ -311,3 +311,228 @@ GOLDEN_SPECS = [
     # short k
     dict(name="k21", n_targets=30, length=150, k=21, n_keys=20_000, seed=15, variant_frac=0.8),
 ]
+
+
+# ---------------------------------------------------------------------------- crossover cases
+# Targets whose graph is known by construction (tests/test_graph_crossover.py, tests/golden/make_golden.py): every
+# (k-1)-mer a pool hands out is distinct from every other ON BOTH STRANDS and none is its own reverse complement, so
+# two nodes overlap only where a case says so and the canonical table never leads a walk onto the opposite strand.
+_RC = str.maketrans("ACGT", "TGCA")
+
+
+def revcomp_str(s):
+    return s[::-1].translate(_RC)
+
+
+class DistinctPool:
+    """Deterministic source of sequences and haplotypes over one set of (k-1)-mers (see above)."""
+
+    def __init__(self, k, seed):
+        self.k = int(k)
+        self.rng = np.random.default_rng(seed)
+        self.seen = set()                      # every (k-1)-mer handed out, and its reverse complement
+
+    def _free(self, mer, also=()):
+        r = revcomp_str(mer)
+        return mer != r and mer not in self.seen and r not in self.seen and mer not in also and r not in also
+
+    def _add(self, mer):
+        self.seen.add(mer)
+        self.seen.add(revcomp_str(mer))
+
+    def grow(self, n):
+        """A new sequence of n >= k - 1 bases, grown base by base (a dead end starts it over)."""
+        k1 = self.k - 1
+        while True:
+            s = "".join("ACGT"[i] for i in self.rng.integers(0, 4, k1))
+            if not self._free(s):
+                continue
+            mine = {s, revcomp_str(s)}
+            while len(s) < n:
+                for b in self.rng.permutation(4):
+                    mer = s[len(s) - k1 + 1:] + "ACGT"[b]
+                    if self._free(mer, mine):
+                        mine.add(mer)
+                        mine.add(revcomp_str(mer))
+                        s += "ACGT"[b]
+                        break
+                else:
+                    break
+            if len(s) == n:
+                self.seen |= mine
+                return s
+
+    def admit(self, own, hap):
+        """Take haplotype `hap` into a case whose forward (k-1)-mers are `own` (a set, extended here): every
+        (k-1)-mer of it that the case does not have yet must be free.  False (and nothing changed) otherwise."""
+        k1 = self.k - 1
+        new, both = [], set()
+        for i in range(len(hap) - k1 + 1):
+            mer = hap[i:i + k1]
+            if mer in own or mer in both:
+                continue
+            if not self._free(mer, both):
+                return False
+            new.append(mer)
+            both.add(mer)
+            both.add(revcomp_str(mer))
+        for mer in new:
+            self._add(mer)
+            own.add(mer)
+        return True
+
+
+def _kmers_of(seq, k):
+    return [seq[i:i + k] for i in range(len(seq) - k + 1)]
+
+
+def _admit_snv(pool, own, seq, pos, step=1, alts=1):
+    """`alts` substitutions of seq at the first position from `pos` on (in steps of `step`) at which they can be
+    admitted.  -> (position, [haplotype, ...])."""
+    while 0 <= pos < len(seq):
+        haps = []
+        trial = set(own)
+        for b in "ACGT":
+            if b != seq[pos] and len(haps) < alts:
+                hap = seq[:pos] + b + seq[pos + 1:]
+                if pool.admit(trial, hap):
+                    haps.append(hap)
+        if len(haps) == alts:
+            own |= trial
+            return pos, haps
+        pos += step                                   # (what a failed position admitted stays taken: harmless)
+    raise AssertionError("no position admits the substitution")
+
+
+def crossover_case(pool, name, length, del_len, extra_ins=0, cov=(60, 35, 30), snvs=True):
+    """One target of `length` bases with a deletion of `del_len` bases whose junction bases differ on both sides (the
+    bubble has k - 1 new nodes, c = k edges, and bypasses b - a = del_len + k reference edges) and three SNVs on the
+    reference background: upstream of the bubble, inside the deleted stretch, downstream of it.  `extra_ins` > 0 adds
+    an insertion of that many bases near the end of the target (more walk nodes than the LDS tier keeps); `snvs`
+    False leaves the deletion alone in its target (the one-bubble shape of k_graph's step 2c).
+    -> dict(name, target, reads [(sequence, coverage)], expect {haplotype name: its new k-mers, in path order})."""
+    k = pool.k
+    T = pool.grow(length)
+    own = set(_kmers_of(T, k - 1))
+    p = 4 * k
+    while True:
+        assert p + del_len + 4 * k < length, "target too short for this deletion"
+        dele = T[:p] + T[p + del_len:]
+        if T[p] != T[p + del_len] and T[p - 1] != T[p + del_len - 1] and pool.admit(own, dele):
+            break
+        p += 1
+    expect = {"del": _kmers_of(dele[p - k + 1:p + k - 1], k)}
+    reads = [(T, cov[0]), (dele, cov[1])]
+    for tag, pos, step in (("up", p - 2 * k, -1), ("in", p + del_len // 2, 1), ("down", p + del_len + 2 * k, 1)) if snvs else ():
+        q, haps = _admit_snv(pool, own, T, pos, step)
+        assert (q + k <= p - k) if tag == "up" else (p + k <= q < p + del_len - k) if tag == "in" else (q >= p + del_len + k and q + k < length)
+        expect[tag] = _kmers_of(haps[0][q - k + 1:q + k], k)
+        reads.append((haps[0], cov[2]))
+    if extra_ins:
+        ins = pool.grow(extra_ins)
+        own |= set(_kmers_of(ins, k - 1))
+        q = length - 2 * k
+        # (junction bases differ on both sides, as for the deletion: every k-mer across a junction is new)
+        while ins[0] == T[q] or ins[-1] == T[q - 1] or not pool.admit(own, T[:q] + ins + T[q:]):
+            q -= 1
+            assert q > p + del_len + 4 * k
+        hap = T[:q] + ins + T[q:]
+        expect["ins"] = _kmers_of(hap[q - k + 1:q + extra_ins + k - 1], k)
+        reads.append((hap, cov[2]))
+    return {"name": name, "target": T, "reads": reads, "expect": expect, "k": k, "kind": "sweep" if snvs else "solo"}
+
+
+def nested_case(pool, name, cov=(60, 35, 35, 30)):
+    """A deletion whose bubble (c1 = k edges) is cheaper than its reference route by 5 hops (b1 - a1 = 100 k + 5),
+    enclosed by a second bubble of c2 = k + 1 edges (a deletion with one base inserted at its junction) that leaves
+    the reference 48 k-mers before a1 and rejoins it 49 k-mers after b1; one SNV upstream of a2, one downstream of b2.
+    In real numbers the route a1 -> inner bubble -> b1 -> b2 beats the outer bubble by 1 - 0.97 = 0.03 at b2, while
+    the reference route a2 -> b2 LOSES to the outer bubble by 0.02: who wins at b2 (and, from the sink, at a2) depends
+    on the true distances of the reference nodes past b1 (before a1), which are not the reference-chain sums.
+    -> like crossover_case; expect has "del" (inner), "outer", "up", "down"."""
+    k = pool.k
+    d1 = 99 * k + 5
+    length = 4 * k + 48 + d1 + 49 + 4 * k + 40
+    T = pool.grow(length)
+    own = set(_kmers_of(T, k - 1))
+    p2 = 4 * k
+    while True:
+        p1, q2 = p2 + 48, p2 + 48 + d1 + 49
+        assert q2 + 4 * k <= length, "target too short"
+        inner = T[:p1] + T[p1 + d1:]
+        ok = T[p1] != T[p1 + d1] and T[p1 - 1] != T[p1 + d1 - 1]
+        outer = None
+        for x in "ACGT" if ok else "":
+            if x != T[p2] and x != T[q2 - 1]:
+                trial = set(own)
+                if pool.admit(trial, inner) and pool.admit(trial, T[:p2] + x + T[q2:]):
+                    own, outer = trial, T[:p2] + x + T[q2:]
+                    break
+        if outer:
+            break
+        p2 += 1
+    expect = {"del": _kmers_of(inner[p1 - k + 1:p1 + k - 1], k), "outer": _kmers_of(outer[p2 - k + 1:p2 + k], k)}
+    reads = [(T, cov[0]), (inner, cov[1]), (outer, cov[2])]
+    for tag, pos, step in (("up", p2 - 2 * k, -1), ("down", q2 + 2 * k, 1)):
+        q, haps = _admit_snv(pool, own, T, pos, step)
+        assert (q + k <= p2 - k) if tag == "up" else (q >= q2 + k and q + k < length)
+        expect[tag] = _kmers_of(haps[0][q - k + 1:q + k], k)
+        reads.append((haps[0], cov[3]))
+    return {"name": name, "target": T, "reads": reads, "expect": expect, "k": k, "kind": "nested"}
+
+
+def tie_case(pool, name, kind, length=None, cov=(60, 35, 30)):
+    """kind "ins3": a 40-base insertion haplotype and two more that carry it with two different substitutions at one
+    inserted position — inside the bubble the walk splits three ways and rejoins, the rejoin node has three
+    in-neighbours at exactly the same distance.  kind "snv2": two substitutions at one reference position."""
+    k = pool.k
+    T = pool.grow(length or 6 * k + 40)
+    own = set(_kmers_of(T, k - 1))
+    p = 3 * k
+    expect = {}
+    if kind == "ins3":
+        while True:
+            ins = pool.grow(40)
+            hap = T[:p] + ins + T[p:]
+            if ins[0] != T[p] and ins[-1] != T[p - 1] and pool.admit(own | set(_kmers_of(ins, k - 1)), hap):
+                break
+        own |= set(_kmers_of(hap, k - 1))
+        q, alts = _admit_snv(pool, own, hap, p + 20, 1, alts=2)
+        assert p + 1 <= q <= p + 38
+        reads = [(T, cov[0]), (hap, cov[1])] + [(h, cov[2]) for h in alts]
+        expect["ins"] = _kmers_of(hap[p - k + 1:p + 40 + k - 1], k)
+        for i, h in enumerate(alts):
+            expect["alt%d" % i] = _kmers_of(h[q - k + 1:q + k], k)
+    else:
+        q, alts = _admit_snv(pool, own, T, p, 1, alts=2)
+        reads = [(T, cov[0])] + [(h, cov[2]) for h in alts]
+        for i, h in enumerate(alts):
+            expect["alt%d" % i] = _kmers_of(h[q - k + 1:q + k], k)
+    return {"name": name, "target": T, "reads": reads, "expect": expect, "k": k, "kind": kind}
+
+
+def records_from_reads(reads, k):
+    """Canonical k-mer records of (sequence, coverage) reads; coverages add up."""
+    acc = {}
+    for seq, c in reads:
+        for key in km.canonical(km.sliding_kmers(km.encode(seq), k), k).tolist():
+            acc[key] = acc.get(key, 0) + c
+    keys = np.array(sorted(acc), dtype=np.uint64)
+    return keys, np.array([acc[x] for x in keys.tolist()], dtype=np.uint32)
+
+
+# 100 c - (b - a) of the crossover sweep: both sides of the closed forms' + 10 margin, the tie, both sides of the
+# crossover of the float32 sums
+CROSSOVER_MARGINS = (12, 11, 10, 9, 8, 3, 1, 0, -1, -2, -5)
+CROSSOVER_GOLDEN = (10, 0, -5)                  # the k = 11 cases make_golden.py runs through the reference
+
+
+def crossover_sweep(k, margins=CROSSOVER_MARGINS, extra_ins=0, seed=0, solo=(), nested=False, length=None):
+    """The cases of the sweep at one k, over one pool (so they can share a table without meeting each other):
+    case i has 100 k - (del_len + k) = margins[i]; after them one deletion-only case per margin of `solo`, then
+    (`nested`) one nested_case.  `length`: of the sweep's targets (default 100 k + 8 k + 100)."""
+    pool = DistinctPool(k, 977 * k + seed)
+    length = (length or 100 * k + 8 * k + 100) + (extra_ins and 4 * k)
+    cases = [crossover_case(pool, "x%d_%+d" % (k, v), length, 99 * k - v, extra_ins) for v in margins]
+    cases += [crossover_case(pool, "solo%d_%+d" % (k, v), length, 99 * k - v, snvs=False) for v in solo]
+    return cases + ([nested_case(pool, "nested%d" % k)] if nested else [])

@@ -404,5 +404,41 @@ def main():
             json.dump(gold, fh)
 
 
+    # ---- 7. the crossover of bubble and reference route (km_amd/synth.py: crossover_sweep; tests/test_graph_crossover.py):
+    #         the k = 11 cases of margin 10, 0 and -5, each alone with a table of its own reads
+    if on("crossover"):
+        sys.path.insert(0, REPO)
+        from km_amd import synth
+        gold = {"cases": []}
+        sweep = synth.crossover_sweep(11)
+        for margin in synth.CROSSOVER_GOLDEN:
+            case = sweep[synth.CROSSOVER_MARGINS.index(margin)]
+            keys, counts = synth.records_from_reads(case["reads"], 11)
+            h = hashlib.md5(case["target"].encode())
+            h.update(keys.tobytes())
+            h.update(counts.tobytes())
+            with tempfile.TemporaryDirectory() as td:
+                fa, dbp = os.path.join(td, case["name"] + ".fa"), os.path.join(td, "reads.jf")
+                with open(fa, "w") as fh:
+                    fh.write(">synthetic:1-%d | name=%s\n%s\n" % (len(case["target"]), case["name"], case["target"]))
+                synth.write_jf(dbp, keys, counts, 11)
+                w, _, wouts = r.stable({"kind": "walk", "targets": [fa], "db": dbp}, cwd=td)
+                g, _, gouts = r.stable({"kind": "graphlog", "targets": [fa], "db": dbp}, cwd=td)
+            t = w["targets"][0]
+            probes = sorted({x["targets"][0].pop("probes") for x in wouts})    # (may move with the seed: the set seen)
+            blobs = [json.dumps(x, sort_keys=True) for x in wouts]
+            st = all(b == blobs[0] for b in blobs)                             # (stable apart from the probe count, kept as a set)
+            gold["cases"].append({"name": case["name"], "margin": margin, "input_md5": h.hexdigest(), "stable_but_probes": st,
+                                  "num_k": t["num_k"], "probes_seen": probes,
+                                  "nodes_md5": hashlib.md5(json.dumps(t["nodes"]).encode()).hexdigest(),
+                                  "path_seqs": t["path_seqs"], "path_min_cov": t["path_min_cov"],
+                                  "removed_ref_edges": [x["targets"][0]["removed_ref_edges"][0] for x in gouts],
+                                  "nonref_edges": [x["targets"][0]["nonref_edges"][0] for x in gouts]})
+            print("crossover", case["name"], "stable" if st else "UNSTABLE", t["num_k"], probes, len(t["path_seqs"]), "paths",
+                  gold["cases"][-1]["removed_ref_edges"], gold["cases"][-1]["nonref_edges"])
+        with open(os.path.join(args.out, "crossover.json"), "w") as fh:
+            json.dump(gold, fh)
+
+
 if __name__ == "__main__":
     main()

@@ -467,6 +467,39 @@ int km_jf_header(int k, int canonical, uint64_t n, uint64_t seed, const char* cm
  * fails after that the partial file is removed. */
 int km_counter_write_jf(km_counter_t* c, const char* path, const char* cmdline_json, uint64_t seed);
 
+/* ---- merging tables that already exist ------------------------------------------------------------
+ * Records of `binary/sorted` files, or of host arrays, go into a counter's table with their counts (DESIGN.md 10,
+ * "Merging tables"): per key the counts are summed, saturating at 2^32 - 1 (KM_MERGE_SUM), or their maximum is
+ * kept (KM_MERGE_MAX); the result does not depend on the order of arrival.  Saturation belongs to this record path
+ * only: counting from reads (add_bases / add_text / add_fastq) keeps its wrapping add.  Reads and records may feed
+ * one counter; km_counter_stats' bases / kmers tally text only, distinct stays exact.  These are this project's own
+ * semantics of "merge", not checked against a run of `jellyfish merge`. */
+#define KM_MERGE_SUM 0
+#define KM_MERGE_MAX 1
+/* Host only, header only: no device is touched, no record is read.  *n_records = the record area's length divided by
+ * the record size (key_bytes + counter_len); any output may be NULL.  KM_E_IO / KM_E_FORMAT / KM_E_K as kmjf_open
+ * gives them for the same file. */
+int km_jf_file_info(const char* path, int32_t* k, int32_t* canonical, uint64_t* n_records, int32_t* key_bytes,
+                    int32_t* counter_len);
+/* n (key, count) pairs; a pair with count 0 is skipped, a key may occur more than once (combined by the mode), and
+ * keys are stored as given: a non-canonical key in a canonical counter stays unreachable by lookups.  Text staged
+ * by an earlier add_bases / add_text is flushed first.  The pairs are packed into file records inside the pinned
+ * staging buffers and enqueued piece by piece; the call returns without waiting for the device.  Before any device
+ * work, the counter left as it was: KM_E_ARG for NULL arguments or a mode other than the two, KM_E_STATE after
+ * km_counter_finish, a sticky FASTQ format error as every add_* returns it.  n == 0 is KM_OK without a launch. */
+int km_counter_add_records(km_counter_t* c, const uint64_t* keys, const uint32_t* counts, uint64_t n, int mode);
+/* The same for the record area of a file, read with pread into the pinned staging buffers piece by piece (whole
+ * records; the file is never in HBM as a whole).  *n_records (may be NULL): the records in the file.  Besides the
+ * above, before any device work: KM_E_IO / KM_E_FORMAT / KM_E_K from the header as kmjf_open gives them, KM_E_ARG
+ * for a file whose k or canonical differs from the counter's (km_last_error names both and the path).  A file
+ * without records is KM_OK without a launch.  KM_E_IO if the file ends before its records do (what was enqueued
+ * before stays added). */
+int km_counter_add_jf(km_counter_t* c, const char* path, int mode, uint64_t* n_records);
+/* Waits for everything added so far.  *records_in: records taken with count > 0 by the two calls above since the
+ * counter was made; *kernel_ms: with KM_COUNT_TIME_MERGE=1 in the environment of km_counter_create, the time of
+ * their kernels by HIP events on the counter's stream, 0 otherwise.  Either may be NULL. */
+int km_counter_merge_stats(km_counter_t* c, uint64_t* records_in, float* kernel_ms);
+
 /* ---- measurement helpers (bench.py at N = 1 holds no device buffers of its own) ------------- */
 int km_device_sync(int device);                                    /* hipDeviceSynchronize on `device`          */
 /* device-to-device copy of `bytes` bytes, `reps` times: read + write GB/s (the box's large-copy

@@ -1,4 +1,4 @@
-"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, and ``count``.
+"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, ``count`` and ``merge``.
 
 Same flags, same ``#key:value`` echo, same TSV and ``#Elapsed time`` trailer as
 km/tools/find_mutation.py:17-60 and km/argparser/find_mutation.py:4-58, so the
@@ -322,6 +322,33 @@ def main_count(args, err=None):
         kc.write_records(args.output, keys, counts, args.mer_len, args.canonical, cmdline=cmdline)
 
 
+def main_merge(args, err=None):
+    """Several .jf files of one k into one on the GPU (km_amd.count.merge_files): per k-mer the counts are summed
+    (saturating at 2^32 - 1) or, with --max, their maximum is kept; the records of the result with count >= -L are
+    written to OUT as `count` writes them (sorted by key, or Jellyfish's own order with --jellyfish-order).  With
+    one input it is a filter and re-writer.  This project's own semantics, not checked against `jellyfish merge`."""
+    err = sys.stderr if err is None else err
+    from . import count as kc
+    mode = "max" if args.max else "sum"
+    db, stats, counter = kc.merge_files(args.inputs, mode=mode, lower_count=args.lower_count, device=default_device(),
+                                        keep_counter=True)
+    cmdline = ["km_amd", "merge", "-L", str(args.lower_count)] + (["--max"] if args.max else []) + (
+        ["--jellyfish-order"] if args.jellyfish_order else []) + ["-o", args.output] + list(args.inputs)
+    try:
+        if args.jellyfish_order:
+            counter.write_jf(args.output, cmdline=cmdline)
+        else:
+            keys, counts = counter.records()
+    finally:
+        counter.close()
+        db.close()
+    for key in ("distinct", "slots", "n_grow", "records_in"):
+        err.write("#%s:%d\n" % (key, stats[key]))
+    err.write("#mode:%s\n" % mode)
+    if not args.jellyfish_order:
+        kc.write_records(args.output, keys, counts, stats["k"], stats["canonical"], cmdline=cmdline)
+
+
 def _one_char(text):
     """argparse type of -Q: exactly one character that is one byte."""
     if len(text) != 1 or ord(text) > 255:
@@ -361,6 +388,13 @@ def build_parser():
                     help="a base of a FASTQ read whose quality character is below CHAR is read as N (FASTQ is then "
                          "parsed on the GPU; no effect on FASTA)")
     ct.add_argument("reads", nargs="+", help="FASTA or FASTQ files, plain or gzip; - is stdin")
+    mg = sub.add_parser("merge", help="sum (or --max) the counts of several .jf files of one k on the GPU -> one .jf")
+    mg.add_argument("-L", "--lower-count", type=int, default=1, help="don't output k-mers with a merged count < lower-count")
+    mg.add_argument("--max", action="store_true", help="keep the maximum count per k-mer instead of the sum")
+    mg.add_argument("-o", "--output", default="mer_counts_merged.jf", help="output file (default: mer_counts_merged.jf)")
+    mg.add_argument("--jellyfish-order", action="store_true",
+                    help="write the records in Jellyfish's own order (matrix position, then key), sorted on the GPU")
+    mg.add_argument("inputs", nargs="+", metavar="db.jf", help="binary/sorted files of one k and one canonical setting")
     return parser
 
 
@@ -385,6 +419,8 @@ def main(argv=None):
         main_linear_kmin(args)
     elif cmd == "count":
         main_count(args)
+    elif cmd == "merge":
+        main_merge(args)
     else:
         parser.print_help(sys.stderr)
         sys.exit(1)

@@ -1,6 +1,9 @@
 """Counting k-mers from read files on the GPU: what `jellyfish count -m k -C -L n -s size reads.fq` does in
 front of every km tool (``python -m km_amd count``).
 
+``merge_files`` sums (or takes the maximum of) the records of existing .jf files into one table on the GPU
+(``python -m km_amd merge``).
+
 ``count_files`` streams FASTA / FASTQ files (plain or gzip) through :class:`km_amd.lib.Counter` and returns the
 database built on the device from the counted records; ``write_records`` writes such records in the file
 framing the readers of this project load, sorted by key; ``write_jellyfish`` writes them in Jellyfish's own
@@ -74,6 +77,47 @@ def count_files(paths, k=31, canonical=True, lower_count=1, device=0, expected_d
         for p in paths:
             feed_file(counter, p, min_qual_char=min_qual_char)
         stats = counter.stats()
+        db = counter.finish(lower_count)
+    except BaseException:
+        counter.close()
+        raise
+    if keep_counter:
+        return db, stats, counter
+    counter.close()
+    return db, stats
+
+
+def merge_files(paths, mode="sum", lower_count=1, device=0, expected_distinct=0, keep_counter=False):
+    """Merge `binary/sorted` files of one k and one canonical setting into one table on the GPU: per key the counts
+    are summed (saturating at 2^32 - 1) or, with mode="max", their maximum is kept; lower_count cuts the RESULT
+    -> (Database, stats), with keep_counter=True (Database, stats, Counter) as count_files.  stats is
+    Counter.stats() before the cut plus k, canonical, mode and records_in (records taken with count > 0).
+
+    Every header is read first (lib.jf_file_info, no GPU): a file whose k or canonical differs from the first
+    file's raises ValueError before a counter exists.  The table is sized from expected_distinct, or else from the
+    largest input's record count, and doubles when the union needs it to.  These are this project's own semantics
+    of "merge", not checked against a run of `jellyfish merge`."""
+    if isinstance(paths, (str, bytes)):
+        paths = [paths]
+    paths = list(paths)
+    if not paths:
+        raise ValueError("no input files")
+    if mode not in _lib.MERGE_MODES:
+        raise ValueError("mode %r is neither 'sum' nor 'max'" % (mode,))
+    infos = [_lib.jf_file_info(p) for p in paths]
+    first = infos[0]
+    for p, info in zip(paths, infos):
+        if (info["k"], info["canonical"]) != (first["k"], first["canonical"]):
+            raise ValueError("%s holds k=%d canonical=%s, but %s (the first file) holds k=%d canonical=%s" % (
+                p, info["k"], info["canonical"], paths[0], first["k"], first["canonical"]))
+    size = int(expected_distinct) or max(info["n_records"] for info in infos)
+    counter = _lib.Counter(k=first["k"], canonical=first["canonical"], device=device, expected_distinct=size)
+    try:
+        for p in paths:
+            counter.add_jf(p, mode=mode)
+        stats = counter.stats()
+        stats.update(k=first["k"], canonical=first["canonical"], mode=mode,
+                     records_in=counter.merge_stats()["records_in"])
         db = counter.finish(lower_count)
     except BaseException:
         counter.close()

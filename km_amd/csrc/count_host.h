@@ -1,5 +1,5 @@
 // count_host.h — km_counter_*, km_text_strip, km_fastq_cut (host part of kmgpu.hip; device side: count_kernel.h,
-// fastq_kernel.h; host helpers: fastx_strip.h, fastq_cut.h)
+// fastq_kernel.h; host helpers: fastx_strip.h, fastq_cut.h; records of existing tables: merge_host.h)
 // ------------------------------------------------------------------ counting k-mers from reads
 // km_counter (include/kmgpu.h): text or bases are staged in two pinned buffers that take turns,
 // copied and inserted (count_kernel.h) on the counter's own stream, so the host strips the next block while the
@@ -55,6 +55,9 @@ struct km_counter {
   std::unique_ptr<FastqDev> fq;           // (after st: its events go before the stream)
   uint64_t fq_offset = 0;                 // bytes km_counter_add_fastq consumed in the earlier calls of this stream
   unsigned long long fq_error = FQ_NO_ERROR;   // what the device found, once read: (stream offset << 8) | kind
+  bool merge_timed = false;               // KM_COUNT_TIME_MERGE: an event pair around every piece's record kernel
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> merge_spans;   // (merge_host.h)
+  float merge_kernel_ms = 0.f;
   km_counter_stats_t last = {0, 0, 0, 0, 0, 0};
   DevBuf<uint64_t> out_keys;
   DevBuf<uint32_t> out_counts;
@@ -62,6 +65,7 @@ struct km_counter {
   ~km_counter() {
     (void)hipSetDevice(device);
     if (st) (void)hipStreamSynchronize(st);
+    for (auto& s : merge_spans) { (void)hipEventDestroy(s.first); (void)hipEventDestroy(s.second); }
   }
 };
 
@@ -170,6 +174,7 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
   c->k = k;
   c->canonical = canonical ? 1 : 0;
   if (const char* e = getenv("KM_COUNT_STAGE_BYTES")) c->stage = std::max<uint64_t>(256, strtoull(e, nullptr, 10));
+  if (const char* e = getenv("KM_COUNT_TIME_MERGE")) c->merge_timed = atoi(e) != 0;
   c->slots = COUNT_DEFAULT_SLOTS;
   if (expected_distinct) {
     c->slots = 64;

@@ -22,7 +22,9 @@ constexpr uint32_t COUNT_RUN = 32;      // window start positions a lane owns
 constexpr uint32_t COUNT_PAD = 128;     // readable bytes behind a staged chunk (the last lane loads 64 from its start)
 // cells of the counter's device meta block (u64 each)
 // (CM_FORMAT: fastq_kernel.h's smallest (stream offset << 8 | kind), ~0 while the text is well-formed)
-enum { CM_DISTINCT = 0, CM_BASES = 1, CM_KMERS = 2, CM_ALLT = 3, CM_ERROR = 4, CM_OUT = 5, CM_FORMAT = 6, CM_WORDS = 8 };
+// (CM_RECORDS: merge_kernel.h's tally of the records taken; CM_BASES / CM_KMERS tally text only)
+enum { CM_DISTINCT = 0, CM_BASES = 1, CM_KMERS = 2, CM_ALLT = 3, CM_ERROR = 4, CM_OUT = 5, CM_FORMAT = 6, CM_RECORDS = 7,
+       CM_WORDS = 8 };
 
 __global__ void k_count_init(CountSlot* slots, uint64_t n_slots) {
   uint4* p = reinterpret_cast<uint4*>(slots);

@@ -9,11 +9,13 @@
 //   kmin_host.h    km_linear_kmin
 //   count_host.h   km_counter_*, km_text_strip, km_fastq_cut
 //   jf_order_host.h  km_jf_*, km_counter_write_jf: files in Jellyfish's own record order
+//   merge_host.h   km_jf_file_info, km_counter_add_records, km_counter_add_jf: records of existing tables
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <sys/mman.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <cerrno>
@@ -40,6 +42,8 @@
 #include "jf_order_kernel.h"
 #include "jf_reader.h"
 #include "kmin_kernel.h"
+#include "merge_kernel.h"
+#include "merge_pieces.h"
 #include "table_kernels.h"
 #include "walk_kernel.h"
 
@@ -53,3 +57,4 @@ using namespace kmd;
 #include "kmin_host.h"
 #include "count_host.h"
 #include "jf_order_host.h"
+#include "merge_host.h"

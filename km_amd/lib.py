@@ -40,6 +40,7 @@ SYMBOLS = [
     "km_counter_add_fastq", "km_fastq_cut", "km_counter_fastq_kernel_ms",
     "km_jf_matrix", "km_jf_sort_records", "km_jf_sort_stats", "km_jf_sort_kernel_ms", "km_jf_header",
     "km_counter_write_jf",
+    "km_jf_file_info", "km_counter_add_records", "km_counter_add_jf", "km_counter_merge_stats",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
 ]
 
@@ -239,6 +240,10 @@ def load():
         "km_jf_sort_kernel_ms": [C.POINTER(C.c_float)],
         "km_jf_header": [i32, i32, u64, u64, cp, vp, u64, C.POINTER(u64), vp, C.POINTER(i32)],
         "km_counter_write_jf": [vp, cp, cp, u64],
+        "km_jf_file_info": [cp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u64), C.POINTER(i32), C.POINTER(i32)],
+        "km_counter_add_records": [vp, vp, vp, u64, i32],
+        "km_counter_add_jf": [vp, cp, i32, C.POINTER(u64)],
+        "km_counter_merge_stats": [vp, C.POINTER(u64), C.POINTER(C.c_float)],
         "km_device_count": [C.POINTER(i32)],
         "km_device_sync": [i32],
         "km_device_copy_GBs": [i32, u64, i32, C.POINTER(dbl)],
@@ -529,6 +534,30 @@ class Counter:
         check(self._lib.km_counter_fastq_kernel_ms(self._c, C.byref(ms)))
         return float(ms.value)
 
+    def add_records(self, keys, counts, mode="sum"):
+        """km_counter_add_records: (key, count) pairs into the table, per key summed (saturating at 2^32 - 1) or
+        the maximum kept (mode "sum" / "max"); pairs with count 0 are skipped, keys may repeat."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        if keys.shape != counts.shape or keys.ndim != 1:
+            raise ValueError("keys and counts must be 1-d arrays of one length")
+        check(self._lib.km_counter_add_records(self._c, ptr(keys) if keys.size else None,
+                                               ptr(counts) if counts.size else None, keys.size, _merge_mode(mode)))
+
+    def add_jf(self, path, mode="sum"):
+        """km_counter_add_jf: the records of a `binary/sorted` file of the counter's k and canonical into the
+        table, combined as by add_records; returns the number of records in the file."""
+        n = C.c_uint64()
+        check(self._lib.km_counter_add_jf(self._c, os.fsencode(path), _merge_mode(mode), C.byref(n)))
+        return int(n.value)
+
+    def merge_stats(self):
+        """km_counter_merge_stats (waits for everything added so far): dict(records_in = records with count > 0
+        taken by add_records / add_jf, kernel_ms = the time of their kernels, needs KM_COUNT_TIME_MERGE=1)."""
+        n, ms = C.c_uint64(), C.c_float()
+        check(self._lib.km_counter_merge_stats(self._c, C.byref(n), C.byref(ms)))
+        return {"records_in": int(n.value), "kernel_ms": float(ms.value)}
+
     def stats(self):
         """dict of km_counter_stats_t (waits for everything added so far)."""
         s = CounterStats()
@@ -556,6 +585,24 @@ class Counter:
         """km_counter_write_jf: the finished counter's records as a file in Jellyfish's own record order, sorted
         on the device and written natively (the records are not copied to the host as arrays)."""
         check(self._lib.km_counter_write_jf(self._c, os.fsencode(path), _cmdline_json(cmdline), int(seed)))
+
+
+MERGE_MODES = {"sum": 0, "max": 1}         # KM_MERGE_SUM, KM_MERGE_MAX
+
+
+def _merge_mode(mode):
+    """The library's code of "sum" / "max"; anything else goes through as an int for the library to refuse."""
+    return MERGE_MODES[mode] if mode in MERGE_MODES else int(mode)
+
+
+def jf_file_info(path):
+    """km_jf_file_info: dict(k, canonical, n_records, key_bytes, counter_len) from the header and the size of a
+    `binary/sorted` file (host only: no record is read)."""
+    k, canonical, kb, cb, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+    check(load().km_jf_file_info(os.fsencode(path), C.byref(k), C.byref(canonical), C.byref(n), C.byref(kb),
+                                 C.byref(cb)))
+    return {"k": int(k.value), "canonical": bool(canonical.value), "n_records": int(n.value),
+            "key_bytes": int(kb.value), "counter_len": int(cb.value)}
 
 
 def _cmdline_json(cmdline):

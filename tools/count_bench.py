@@ -20,6 +20,11 @@ timed as wall time around calls that end in km_counter_stats (which waits for th
                kernels alone (position, scan, scatter, sort; HIP events inside the call) and the bucket figures;
                and beside them the path it replaces for a key-sorted file: Counter.records() + write_records,
                which sorts with np.argsort (host_sorted_*).  Files go to /dev/shm if there is one, else to the temp directory.
+  merge      - the two halves of the reads counted separately and written as two files (Counter.write_jf), then
+               Counter.add_jf of both into a counter sized as merge_files sizes it: wall time to km_counter_stats,
+               input records/s, the time of the record kernel by HIP events (KM_COUNT_TIME_MERGE), best and all of
+               --write-reps runs; and beside it the host path a user has today: Database.open(..).records() of both
+               files combined with np.unique + np.add.at (host_merge_*)
 and km_device_copy_GBs of the same run for scale.
 
 usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31] [--write-reps 3] [--text-reps 3]
@@ -165,6 +170,59 @@ def time_writers(counter, k, reps):
     }
 
 
+def time_merge(stream, k, device, reps):
+    """The field group of merging: two files from the halves of the reads, add_jf of both against the host path."""
+    os.environ["KM_COUNT_TIME_MERGE"] = "1"
+    tmp = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else tempfile.gettempdir()
+    paths = [os.path.join(tmp, "count_bench_%d_half%d.jf" % (os.getpid(), i)) for i in range(2)]
+    half = stream.size // 2
+    half -= half % 101                                   # (a read and its newline: the cut falls between reads)
+    try:
+        for path, part in zip(paths, (stream[:half], stream[half:])):
+            c = kmlib.Counter(k=k, device=device)
+            c.add_bases(part)
+            c.finish(1).close()
+            c.write_jf(path)
+            c.close()
+        n_in = [kmlib.jf_file_info(p)["n_records"] for p in paths]
+        wall, kernel, host, parts = [], [], [], None
+        for _ in range(reps):
+            c = kmlib.Counter(k=k, device=device, expected_distinct=max(n_in))
+            t0 = time.perf_counter()
+            for p in paths:
+                c.add_jf(p)
+            st = c.stats()
+            wall.append(time.perf_counter() - t0)
+            kernel.append(c.merge_stats()["kernel_ms"])
+            c.close()
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            recs = []
+            for p in paths:
+                db = kmlib.Database.open(p)
+                recs.append(db.records())
+                db.close()
+            t1 = time.perf_counter()
+            keys, inverse = np.unique(np.concatenate([r[0] for r in recs]), return_inverse=True)
+            total = np.zeros(keys.size, np.uint64)
+            np.add.at(total, inverse, np.concatenate([r[1] for r in recs]))
+            t2 = time.perf_counter()
+            host.append(t2 - t0)
+            if parts is None or host[-1] <= min(host):
+                parts = {"open_records_s": t1 - t0, "unique_add_s": t2 - t1}
+        assert keys.size == st["distinct"]
+    finally:
+        for p in paths:
+            if os.path.exists(p):
+                os.unlink(p)
+    return {"merge": {
+        "reps": reps, "dir": tmp, "records_in": n_in, "distinct": st["distinct"], "n_grow": st["n_grow"],
+        "table_slots": st["slots"], "add_jf_s": min(wall), "add_jf_s_all": wall,
+        "add_jf_records_per_s": sum(n_in) / min(wall), "add_jf_kernel_ms": min(kernel), "add_jf_kernel_ms_all": kernel,
+        "host_merge_s": min(host), "host_merge_s_all": host, "host_merge_parts": parts,
+    }}
+
+
 def run_size(name, k, device, rng, write_reps=3, text_reps=3):
     genome_len, n_reads, stage = SIZES[name]
     if stage:
@@ -191,6 +249,7 @@ def run_size(name, k, device, rng, write_reps=3, text_reps=3):
     writers = time_writers(sized, k, write_reps)
     sized.close()
 
+    merged = time_merge(stream, k, device, write_reps)
     text_paths, st_text = time_text_paths(k, device, text, text_reps)
     assert (st_text["kmers"], st_text["distinct"]) == (st["kmers"], st["distinct"])
     traffic = 12 * st["kmers"] + 8 * st["distinct"]
@@ -203,6 +262,7 @@ def run_size(name, k, device, rng, write_reps=3, text_reps=3):
         **text_paths,
         "finish_s": t_finish,
         **writers,
+        **merged,
     }
 
 

@@ -8,6 +8,8 @@
 // piece i covers [i (S - k + 1), i (S - k + 1) + S), so a window of k bytes lies wholly inside exactly one piece.
 // km_counter_add_fastq stages raw FASTQ text instead, in pieces of whole records that overlap by nothing, and the
 // device turns each piece into such a byte stream of its own (fastq_kernel.h) in front of the same insert kernel.
+// Whatever is staged, text, FASTQ or the records of merge_host.h, takes one way to the device: Staging::claim, fill
+// Staging::mine, counter_ship, then the producer's own kernels.
 namespace {
 constexpr uint64_t COUNT_STAGE_BYTES = 16ull << 20;     // per pinned buffer (KM_COUNT_STAGE_BYTES: tests)
 constexpr uint64_t COUNT_DEFAULT_SLOTS = 1ull << 16;
@@ -18,10 +20,24 @@ struct FastqDev {
   DevBuf<uint8_t> masked;                 // the piece as k_count_insert reads it (k_fq_mask's output)
   DevBuf<uint32_t> tiles, sums;           // newlines per tile, scanned in place (k_scan_*), and the chunk sums
   DevBuf<uint32_t> line_start;
-  bool timed = false;                     // KM_COUNT_TIME_FASTQ: an event pair around every piece's kernels
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> spans;
-  float kernel_ms = 0.f;
-  ~FastqDev() { for (auto& s : spans) { (void)hipEventDestroy(s.first); (void)hipEventDestroy(s.second); } }
+};
+
+// The two pinned buffers through which everything reaches the device, taking turns.  One rule holds them together:
+// the host writes a buffer only once the copy out of it is done.  Producers write through `mine` alone: claim() sets
+// it once the buffer whose turn it is has been waited for, counter_ship takes it away again, and it is null in
+// between, so no producer can write under a copy.  (km_counter_write_jf runs the same buffers and events the other
+// way, device to host, once the counter has finished.)
+struct Staging {
+  Pinned pin[2];
+  Event copied[2];                        // the copy out of pin[i] is done
+  uint64_t bytes = COUNT_STAGE_BYTES;     // per buffer
+  int cur = 0;                            // whose turn it is
+  unsigned char* mine = nullptr;          // pin[cur] while it is the host's to write
+  int claim() {
+    HIPCHK(hipEventSynchronize(copied[cur]));
+    mine = pin[cur];
+    return KM_OK;
+  }
 };
 
 const char* fastq_error_text(unsigned kind) {
@@ -42,22 +58,18 @@ struct km_counter {
   uint64_t slots = 0;
   DevBuf<unsigned long long> meta;        // CM_* cells
   DevBuf<uint8_t> d_text;                 // the staged piece on the device (one: copy and kernel are stream-ordered)
-  Pinned pin[2];
-  Event copied[2];                        // the copy out of pin[i] is done: the host may write it again
-  uint64_t stage = COUNT_STAGE_BYTES;
-  int cur = 0;
-  uint64_t fill = 0;                      // bytes in pin[cur]
+  Staging stg;
+  uint64_t fill = 0;                      // bytes of add_bases / add_text in stg.mine
   uint32_t own_from = 0;                  // of those, carried over from the piece before
   uint64_t occ_ub = 0;                    // upper bound of the occupied slots once everything enqueued has run
   uint32_t n_grow = 0;
   bool finished = false;
   km_text_state_t text = {0, 0, 0, 0, 0};
-  std::unique_ptr<FastqDev> fq;           // (after st: its events go before the stream)
+  std::unique_ptr<FastqDev> fq;
+  KernelSpans fq_spans;                   // KM_COUNT_TIME_FASTQ: around every piece's line-table and mask kernels
   uint64_t fq_offset = 0;                 // bytes km_counter_add_fastq consumed in the earlier calls of this stream
   unsigned long long fq_error = FQ_NO_ERROR;   // what the device found, once read: (stream offset << 8) | kind
-  bool merge_timed = false;               // KM_COUNT_TIME_MERGE: an event pair around every piece's record kernel
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> merge_spans;   // (merge_host.h)
-  float merge_kernel_ms = 0.f;
+  KernelSpans merge_spans;                // KM_COUNT_TIME_MERGE: around every piece's record kernel (merge_host.h)
   km_counter_stats_t last = {0, 0, 0, 0, 0, 0};
   DevBuf<uint64_t> out_keys;
   DevBuf<uint32_t> out_counts;
@@ -65,7 +77,6 @@ struct km_counter {
   ~km_counter() {
     (void)hipSetDevice(device);
     if (st) (void)hipStreamSynchronize(st);
-    for (auto& s : merge_spans) { (void)hipEventDestroy(s.first); (void)hipEventDestroy(s.second); }
   }
 };
 
@@ -73,6 +84,13 @@ struct km_counter {
 static int counter_format_failed(const km_counter* c) {
   return fail(KM_E_FORMAT, "%s at byte offset %llu", fastq_error_text((unsigned)(c->fq_error & 0xFF)),
               (unsigned long long)(c->fq_error >> 8));
+}
+
+// What every call that feeds or ends a counter checks once its arguments are in order.
+static int counter_usable(const km_counter* c) {
+  if (c->finished) return fail(KM_E_STATE, "counter already finished");
+  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
+  return KM_OK;
 }
 
 // waits for everything enqueued
@@ -126,35 +144,61 @@ static int counter_reserve(km_counter* c, uint64_t windows) {
   return KM_OK;
 }
 
-// Enqueue the piece in pin[cur] (copy + insert) and turn to the other buffer, which starts with the last k - 1
-// bytes of this one.  Nothing to do while the buffer holds only such carried bytes.
+// The n bytes the host wrote to the claimed buffer go to d_text, and the turn passes to the other buffer.
+// new_keys: the most keys the piece can add (counter_reserve, which may wait for the stream and rehash first).
+static int counter_ship(km_counter* c, uint64_t n, uint64_t new_keys) {
+  Staging& s = c->stg;
+  KMCHK(counter_reserve(c, new_keys));
+  HIPCHK(hipMemcpyAsync(c->d_text, s.mine, n, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipEventRecord(s.copied[s.cur], c->st));
+  s.mine = nullptr;
+  s.cur ^= 1;
+  return KM_OK;
+}
+
+// text[0 .. n) on the device into the table; the windows that start before own_from belong to the piece before.
+static int launch_insert(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from) {
+  const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
+  hipLaunchKernelGGL(k_count_insert, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, c->st, text, n, own_from,
+                     c->k, c->canonical, c->table.p, c->slots - 1, c->meta.p);
+  HIPCHK(hipGetLastError());
+  return KM_OK;
+}
+
+// Enqueue the piece of add_bases / add_text (copy + insert) and turn to the other buffer, which starts with the
+// last k - 1 bytes of this one.  Nothing to do while the buffer holds only such carried bytes.
 static int counter_flush(km_counter* c) {
   if (c->fill <= c->own_from) return KM_OK;
   const uint64_t n = c->fill;
-  KMCHK(counter_reserve(c, n >= (uint64_t)c->k ? n - c->k + 1 : 0));
-  HIPCHK(hipMemcpyAsync(c->d_text, c->pin[c->cur], n, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipEventRecord(c->copied[c->cur], c->st));
-  const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
-  hipLaunchKernelGGL(k_count_insert, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, c->st, c->d_text.p, n,
-                     c->own_from, c->k, c->canonical, c->table.p, c->slots - 1, c->meta.p);
-  HIPCHK(hipGetLastError());
-  const int nxt = c->cur ^ 1;
-  HIPCHK(hipEventSynchronize(c->copied[nxt]));
+  const unsigned char* sent = c->stg.mine;            // (a buffer whose copy is in flight may still be read)
+  KMCHK(counter_ship(c, n, n >= (uint64_t)c->k ? n - c->k + 1 : 0));
+  KMCHK(launch_insert(c, c->d_text, n, c->own_from));
+  KMCHK(c->stg.claim());
   const uint64_t keep = std::min<uint64_t>((uint64_t)c->k - 1, n);
-  memcpy(c->pin[nxt], c->pin[c->cur] + n - keep, keep);
+  memcpy(c->stg.mine, sent + n - keep, keep);
   c->fill = keep;
   c->own_from = (uint32_t)keep;
-  c->cur = nxt;
+  return KM_OK;
+}
+
+// In front of a run of whole pieces (FASTQ records, records of a table): what add_bases / add_text left goes first,
+// and the k - 1 bytes it would carry over are dropped, since no k-mer spans a change between the kinds of calls.
+// Every piece of the run claims its own buffer, and so does counter_append when its turn comes again.
+static int counter_begin_pieces(km_counter* c) {
+  KMCHK(counter_flush(c));
+  c->fill = 0;
+  c->own_from = 0;
   return KM_OK;
 }
 
 static int counter_append(km_counter* c, const uint8_t* p, uint64_t n) {
   while (n) {
-    if (c->fill == c->stage) {
+    if (c->fill == c->stg.bytes) {
       KMCHK(counter_flush(c));
     }
-    const uint64_t take = std::min(n, c->stage - c->fill);
-    memcpy(c->pin[c->cur] + c->fill, p, take);
+    if (!c->stg.mine) KMCHK(c->stg.claim());            // the first bytes, or the first after a run of whole pieces
+    const uint64_t take = std::min(n, c->stg.bytes - c->fill);
+    memcpy(c->stg.mine + c->fill, p, take);
     c->fill += take;
     p += take;
     n -= take;
@@ -173,8 +217,9 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
   c->device = device;
   c->k = k;
   c->canonical = canonical ? 1 : 0;
-  if (const char* e = getenv("KM_COUNT_STAGE_BYTES")) c->stage = std::max<uint64_t>(256, strtoull(e, nullptr, 10));
-  if (const char* e = getenv("KM_COUNT_TIME_MERGE")) c->merge_timed = atoi(e) != 0;
+  Staging& s = c->stg;
+  if (const char* e = getenv("KM_COUNT_STAGE_BYTES")) s.bytes = std::max<uint64_t>(256, strtoull(e, nullptr, 10));
+  if (const char* e = getenv("KM_COUNT_TIME_MERGE")) c->merge_spans.timed = atoi(e) != 0;
   c->slots = COUNT_DEFAULT_SLOTS;
   if (expected_distinct) {
     c->slots = 64;
@@ -183,12 +228,12 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
   HIPCHK(hipStreamCreateWithFlags(&c->st.h, hipStreamNonBlocking));
   int rc = c->table.alloc(c->slots);
   if (rc == KM_OK) rc = c->meta.alloc(CM_WORDS);
-  if (rc == KM_OK) rc = c->d_text.alloc(c->stage + COUNT_PAD);
+  if (rc == KM_OK) rc = c->d_text.alloc(s.bytes + COUNT_PAD);
   if (rc != KM_OK) return rc;
   for (int i = 0; i < 2; ++i) {
-    hipError_t e = hipHostMalloc((void**)&c->pin[i].h, c->stage + COUNT_PAD, hipHostMallocDefault);
-    if (e != hipSuccess) { c->pin[i].h = nullptr; return fail(KM_E_NOMEM, "pinned staging buffer: %s", hipGetErrorString(e)); }
-    HIPCHK(hipEventCreateWithFlags(&c->copied[i].h, hipEventDisableTiming));
+    hipError_t e = hipHostMalloc((void**)&s.pin[i].h, s.bytes + COUNT_PAD, hipHostMallocDefault);
+    if (e != hipSuccess) { s.pin[i].h = nullptr; return fail(KM_E_NOMEM, "pinned staging buffer: %s", hipGetErrorString(e)); }
+    HIPCHK(hipEventCreateWithFlags(&s.copied[i].h, hipEventDisableTiming));
   }
   HIPCHK(hipMemsetAsync(c->meta, 0, CM_WORDS * 8, c->st));
   HIPCHK(hipMemsetAsync(c->meta.p + CM_FORMAT, 0xFF, 8, c->st));        // FQ_NO_ERROR
@@ -202,8 +247,7 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
 
 extern "C" int km_counter_add_bases(km_counter_t* c, const uint8_t* bytes, uint64_t n) {
   if (!c || (n && !bytes)) return fail(KM_E_ARG, "null argument");
-  if (c->finished) return fail(KM_E_STATE, "counter already finished");
-  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
+  KMCHK(counter_usable(c));
   if (n == 0) return KM_OK;
   HIPCHK(hipSetDevice(c->device));
   int rc = counter_append(c, bytes, n);
@@ -232,8 +276,7 @@ int strip_failed(const kmstrip::Result& r) {
 
 extern "C" int km_counter_add_text(km_counter_t* c, const char* text, uint64_t n, int final, uint64_t* consumed) {
   if (!c || !consumed || (n && !text)) return fail(KM_E_ARG, "null argument");
-  if (c->finished) return fail(KM_E_STATE, "counter already finished");
-  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
+  KMCHK(counter_usable(c));
   *consumed = 0;
   if (n == 0 && !final) return KM_OK;
   HIPCHK(hipSetDevice(c->device));
@@ -248,17 +291,18 @@ extern "C" int km_counter_add_text(km_counter_t* c, const char* text, uint64_t n
 // ---- raw FASTQ text, parsed on the device
 static int fastq_prepare(km_counter* c) {
   if (c->fq) return KM_OK;
-  if (c->stage >= 0xFFFFFFF0ull) return fail(KM_E_ARG, "staging buffers of %llu bytes: the line table is 32-bit",
-                                             (unsigned long long)c->stage);
+  const uint64_t stage = c->stg.bytes;
+  if (stage >= 0xFFFFFFF0ull) return fail(KM_E_ARG, "staging buffers of %llu bytes: the line table is 32-bit",
+                                          (unsigned long long)stage);
   std::unique_ptr<FastqDev> f(new (std::nothrow) FastqDev);
   if (!f) return fail(KM_E_NOMEM, "host allocation failed");
-  const uint64_t max_tiles = (c->stage + FQ_TILE - 1) / FQ_TILE;
+  const uint64_t max_tiles = (stage + FQ_TILE - 1) / FQ_TILE;
   const uint64_t max_chunks = (max_tiles + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK;
-  KMCHK(f->masked.alloc(c->stage + COUNT_PAD));
+  KMCHK(f->masked.alloc(stage + COUNT_PAD));
   KMCHK(f->tiles.alloc(max_chunks * SCAN_CHUNK));
   KMCHK(f->sums.alloc(max_chunks));
-  KMCHK(f->line_start.alloc(c->stage + 2));           // a piece of n bytes has at most n newlines
-  if (const char* e = getenv("KM_COUNT_TIME_FASTQ")) f->timed = atoi(e) != 0;
+  KMCHK(f->line_start.alloc(stage + 2));              // a piece of n bytes has at most n newlines
+  if (const char* e = getenv("KM_COUNT_TIME_FASTQ")) c->fq_spans.timed = atoi(e) != 0;
   c->fq = std::move(f);
   return KM_OK;
 }
@@ -267,22 +311,12 @@ static int fastq_prepare(km_counter* c) {
 // counter's stream.  base: the piece's offset in the stream (for what the validation reports).
 static int fastq_enqueue(km_counter* c, const char* text, uint64_t n, uint64_t base, uint32_t min_qual) {
   FastqDev& f = *c->fq;
-  HIPCHK(hipEventSynchronize(c->copied[c->cur]));
-  memcpy(c->pin[c->cur], text, n);
-  KMCHK(counter_reserve(c, n));                         // every byte taken as a window: a bound, and a loose one
-  HIPCHK(hipMemcpyAsync(c->d_text, c->pin[c->cur], n, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipEventRecord(c->copied[c->cur], c->st));
-  c->cur ^= 1;
+  KMCHK(c->stg.claim());
+  memcpy(c->stg.mine, text, n);
+  KMCHK(counter_ship(c, n, n));                         // every byte taken as a window: a bound, and a loose one
   const uint32_t n_tiles = (uint32_t)((n + FQ_TILE - 1) / FQ_TILE);
   const uint32_t n_chunks = (uint32_t)(((uint64_t)n_tiles + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK);
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  if (f.timed) {
-    HIPCHK(hipEventCreate(&t0));
-    hipError_t e = hipEventCreate(&t1);
-    if (e != hipSuccess) { (void)hipEventDestroy(t0); return fail_hip(KM_E_HIP, "hipEventCreate", e); }
-    f.spans.emplace_back(t0, t1);
-    HIPCHK(hipEventRecord(t0, c->st));
-  }
+  KMCHK(c->fq_spans.open(c->st));
   HIPCHK(hipMemsetAsync(f.tiles, 0, (uint64_t)n_chunks * SCAN_CHUNK * 4, c->st));
   hipLaunchKernelGGL(k_fq_count_lines, dim3(n_tiles), dim3(FQ_THREADS), 0, c->st, c->d_text.p, n, f.tiles.p);
   hipLaunchKernelGGL(k_scan_reduce, dim3(n_chunks), dim3(SCAN_THREADS), 0, c->st, f.tiles.p, f.sums.p);
@@ -293,12 +327,8 @@ static int fastq_enqueue(km_counter* c, const char* text, uint64_t n, uint64_t b
   hipLaunchKernelGGL(k_fq_mask, dim3(n_tiles), dim3(FQ_THREADS), 0, c->st, c->d_text.p, n, f.tiles.p, n_tiles,
                      f.line_start.p, min_qual, base, f.masked.p, c->meta.p + CM_FORMAT);
   HIPCHK(hipGetLastError());
-  if (f.timed) HIPCHK(hipEventRecord(t1, c->st));
-  const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
-  hipLaunchKernelGGL(k_count_insert, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, c->st, f.masked.p, n, 0u,
-                     c->k, c->canonical, c->table.p, c->slots - 1, c->meta.p);
-  HIPCHK(hipGetLastError());
-  return KM_OK;
+  KMCHK(c->fq_spans.close(c->st));
+  return launch_insert(c, f.masked, n, 0);
 }
 
 extern "C" int km_fastq_cut(const char* text, uint64_t n, uint64_t* cut) {
@@ -311,32 +341,26 @@ extern "C" int km_counter_add_fastq(km_counter_t* c, const char* text, uint64_t 
                                     uint64_t* consumed) {
   if (!c || !consumed || (n && !text)) return fail(KM_E_ARG, "null argument");
   if (min_qual_char < 0 || min_qual_char > 255) return fail(KM_E_ARG, "min_qual_char %d outside 0..255", min_qual_char);
-  if (c->finished) return fail(KM_E_STATE, "counter already finished");
-  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
+  KMCHK(counter_usable(c));
   *consumed = 0;
   const uint64_t end = final ? n : kmcut::cut(text, n);
   if (end) {
     HIPCHK(hipSetDevice(c->device));
     KMCHK(fastq_prepare(c));
-    // what add_bases / add_text left goes first; the bytes it would carry over are dropped: no k-mer spans a
-    // change between the two kinds of calls
-    KMCHK(counter_flush(c));
-    c->fill = 0;
-    c->own_from = 0;
+    KMCHK(counter_begin_pieces(c));
   }
   for (uint64_t pos = 0; pos < end;) {
     uint64_t take = end - pos;
-    if (take > c->stage) {
-      take = kmcut::cut(text + pos, c->stage);
+    if (take > c->stg.bytes) {
+      take = kmcut::cut(text + pos, c->stg.bytes);
       if (take == 0)
         return fail(KM_E_CAPACITY, "no FASTQ record ends within the %llu bytes of a staging buffer from byte offset %llu",
-                    (unsigned long long)c->stage, (unsigned long long)(c->fq_offset + pos));
+                    (unsigned long long)c->stg.bytes, (unsigned long long)(c->fq_offset + pos));
     }
     KMCHK(fastq_enqueue(c, text + pos, take, c->fq_offset + pos, (uint32_t)min_qual_char));
     pos += take;
     *consumed = pos;
   }
-  if (end) HIPCHK(hipEventSynchronize(c->copied[c->cur]));     // add_bases / add_text write pin[cur] without asking
   c->fq_offset = final ? 0 : c->fq_offset + end;
   return KM_OK;
 }
@@ -344,19 +368,10 @@ extern "C" int km_counter_add_fastq(km_counter_t* c, const char* text, uint64_t 
 extern "C" int km_counter_fastq_kernel_ms(km_counter_t* c, float* ms) {
   if (!c || !ms) return fail(KM_E_ARG, "null argument");
   *ms = 0.f;
-  if (!c->fq) return KM_OK;
+  if (!c->fq_spans.timed) return KM_OK;
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->st));
-  for (auto& s : c->fq->spans) {
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, s.first, s.second));
-    c->fq->kernel_ms += t;
-    (void)hipEventDestroy(s.first);
-    (void)hipEventDestroy(s.second);
-  }
-  c->fq->spans.clear();
-  *ms = c->fq->kernel_ms;
-  return KM_OK;
+  return c->fq_spans.drain(ms);
 }
 
 extern "C" int km_text_strip(km_text_state_t* st, const char* text, uint64_t n, int final, uint8_t* out, uint64_t cap,
@@ -389,8 +404,7 @@ extern "C" int km_counter_stats(km_counter_t* c, km_counter_stats_t* s) {
 
 extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t** out) {
   if (!c || !out) return fail(KM_E_ARG, "null argument");
-  if (c->finished) return fail(KM_E_STATE, "counter already finished");
-  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
+  KMCHK(counter_usable(c));
   HIPCHK(hipSetDevice(c->device));
   int rc = counter_flush(c);
   unsigned long long m[CM_WORDS];
@@ -422,7 +436,7 @@ extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t**
   c->n_out = n;
   c->table.release();
   c->d_text.release();
-  if (c->fq) { c->fq->masked.release(); c->fq->tiles.release(); c->fq->sums.release(); c->fq->line_start.release(); }
+  c->fq.reset();
   c->finished = true;
   *out = h;
   return KM_OK;

@@ -74,15 +74,28 @@ static TableView view_of(const kmjf* h) {
   return t;
 }
 
+// What jfio's readers return, as the library's codes under the reader's own message; then the k this library takes.
+static int reader_result(int rc, const std::string& err, int k) {
+  if (rc != 0) return fail(rc == 1 ? KM_E_IO : rc == 2 ? KM_E_FORMAT : KM_E_K, "%s", err.c_str());
+  if (k < 2 || k > 32) return fail(KM_E_K, "k=%d unsupported", k);
+  return KM_OK;
+}
+
+// The header of `path` as kmjf_open judges it; *f is left open, positioned anywhere.
+static int open_layout(const char* path, jfio::Layout* lay, File* f) {
+  std::string err;
+  void* file = nullptr;
+  const int rc = jfio::read_layout(path, lay, &file, &err);
+  f->h = static_cast<FILE*>(file);
+  return reader_result(rc, err, lay->k);
+}
+
 extern "C" int kmjf_open(const char* path, kmjf_t** out) {
   if (!path || !out) return fail(KM_E_ARG, "null argument");
   jfio::Records rec;
   std::string err;
-  int rc = jfio::read_file(path, &rec, &err);
-  if (rc == 1) return fail(KM_E_IO, "%s", err.c_str());
-  if (rc == 2) return fail(KM_E_FORMAT, "%s", err.c_str());
-  if (rc == 3) return fail(KM_E_K, "%s", err.c_str());
-  if (rec.k < 2 || rec.k > 32) return fail(KM_E_K, "k=%d unsupported", rec.k);
+  const int rc = jfio::read_file(path, &rec, &err);
+  KMCHK(reader_result(rc, err, rec.k));
   kmjf* h = new (std::nothrow) kmjf;
   if (!h) return fail(KM_E_NOMEM, "host allocation failed");
   h->k = rec.k;
@@ -480,14 +493,9 @@ extern "C" int kmjf_broadcast(kmjf_t* h, const int* devices, int n, kmjf_t** rep
 extern "C" int kmjf_load(const char* path, int device, kmjf_t** out) {
   if (!path || !out) return fail(KM_E_ARG, "null argument");
   jfio::Layout lay;
-  std::string err;
-  void* file = nullptr;
-  int rc = jfio::read_layout(path, &lay, &file, &err);
-  if (rc == 1) return fail(KM_E_IO, "%s", err.c_str());
-  if (rc == 2) return fail(KM_E_FORMAT, "%s", err.c_str());
-  if (rc == 3) return fail(KM_E_K, "%s", err.c_str());
-  File f(static_cast<FILE*>(file));
-  if (lay.k < 2 || lay.k > 32) return fail(KM_E_K, "k=%d unsupported", lay.k);
+  File f;
+  int rc = open_layout(path, &lay, &f);
+  if (rc != KM_OK) return rc;
   const uint64_t n = lay.n_records;
   const uint64_t rec = (uint64_t)lay.key_bytes + lay.counter_bytes;
   const uint64_t body = n * rec;

@@ -97,9 +97,11 @@ struct Owned {
   explicit Owned(H v = nullptr) : h(v) {}
   Owned(const Owned&) = delete;
   Owned& operator=(const Owned&) = delete;
+  Owned(Owned&& o) noexcept : h(o.take()) {}
   ~Owned() { reset(); }
   operator H() const { return h; }
   void reset() { if (h) (void)Free(h); h = nullptr; }
+  H take() { H v = h; h = nullptr; return v; }     // the handle, from now on the caller's to free
 };
 using Event = Owned<hipEvent_t, hipEventDestroy>;
 using Stream = Owned<hipStream_t, hipStreamDestroy>;
@@ -109,6 +111,38 @@ using Pinned = Owned<unsigned char*, hipHostFree>;
 using File = Owned<FILE*, fclose>;
 struct Unmap { size_t len; void operator()(void* p) const { munmap(p, len); } };
 using Mapping = std::unique_ptr<void, Unmap>;
+
+// Timing of kernels that an environment variable asks for: an event pair around each run of them on one stream.
+// Does nothing unless `timed`.  The owner declares it after its stream: the events go before the stream.
+struct KernelSpans {
+  bool timed = false;
+  std::vector<std::pair<Event, Event>> pairs;      // recorded and not yet drained
+  float ms = 0.f;                                  // of the pairs drained so far
+  int open(hipStream_t st) {
+    if (!timed) return KM_OK;
+    Event t0, t1;
+    HIPCHK(hipEventCreate(&t0.h));
+    HIPCHK(hipEventCreate(&t1.h));
+    pairs.emplace_back(std::move(t0), std::move(t1));
+    HIPCHK(hipEventRecord(pairs.back().first, st));
+    return KM_OK;
+  }
+  int close(hipStream_t st) {
+    if (timed) HIPCHK(hipEventRecord(pairs.back().second, st));
+    return KM_OK;
+  }
+  // (the stream has been waited for)  *total = the time of every pair so far
+  int drain(float* total) {
+    for (auto& p : pairs) {
+      float t = 0.f;
+      HIPCHK(hipEventElapsedTime(&t, p.first, p.second));
+      ms += t;
+    }
+    pairs.clear();
+    *total = ms;
+    return KM_OK;
+  }
+};
 }  // namespace
 
 // ---- streams.  A pipelined consumer runs a few batches at a time, each on its own launch stream.  How
@@ -141,7 +175,7 @@ int pool_get(int device, hipStream_t* out) {
   if (p.launch.empty()) {
     Stream made[POOL_STREAMS];                     // the pool takes them once all exist
     for (Stream& s : made) HIPCHK(hipStreamCreateWithFlags(&s.h, hipStreamNonBlocking));
-    for (Stream& s : made) { p.launch.push_back(s.h); s.h = nullptr; }
+    for (Stream& s : made) p.launch.push_back(s.take());
     p.in_use.assign(p.launch.size(), 0);
   }
   for (size_t i = 0; i < p.launch.size(); ++i)

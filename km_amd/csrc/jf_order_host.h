@@ -60,14 +60,13 @@ int jf_sort_device(const uint64_t* columns, int k, int size_log2, const uint64_t
   KMCHK(cursor.alloc(n_buckets));
   KMCHK(sums.alloc(n_chunks));
   KMCHK(d_stats.alloc(2));
-  Event t0, t1;
-  HIPCHK(hipEventCreate(&t0.h));
-  HIPCHK(hipEventCreate(&t1.h));
+  KernelSpans span;
+  span.timed = true;
   HIPCHK(hipMemcpyAsync(d_cols, columns, (size_t)c * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(dir, 0, dir_words * 4, st));
   HIPCHK(hipMemsetAsync(cursor, 0, (uint64_t)n_buckets * 4, st));
   HIPCHK(hipMemsetAsync(d_stats, 0, 16, st));
-  HIPCHK(hipEventRecord(t0, st));
+  KMCHK(span.open(st));
   const int grid = grid_for(n, JF_THREADS);
   hipLaunchKernelGGL(k_jf_position, dim3(grid), dim3(JF_THREADS), 0, st, d_cols.p, c, mask, d_keys, n, pos.p, dir.p,
                      shift, bits);
@@ -80,11 +79,11 @@ int jf_sort_device(const uint64_t* columns, int k, int size_log2, const uint64_t
   hipLaunchKernelGGL(k_jf_sort_buckets, dim3(std::min<uint32_t>(n_buckets, 1u << 20)), dim3(JF_THREADS), 0, st, dir.p,
                      n_buckets, pos2.p, keys2.p, counts2.p, (uint32_t)((c + 7) / 8), d_records, d_pos_out);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(t1, st));
+  KMCHK(span.close(st));
   unsigned long long stats[2];
   HIPCHK(hipMemcpyAsync(stats, d_stats, 16, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipEventElapsedTime(&g_jf_kernel_ms, t0, t1));
+  KMCHK(span.drain(&g_jf_kernel_ms));
   g_jf_stats[0] = n_buckets;
   g_jf_stats[1] = stats[0];
   g_jf_stats[2] = stats[1];
@@ -242,23 +241,22 @@ extern "C" int km_counter_write_jf(km_counter_t* c, const char* path, const char
     return false;
   };
   bool ok = put(header.data(), header.size());
-  const uint64_t piece = c->stage;
+  Staging& s = c->stg;
+  const uint64_t piece = s.bytes;
   auto enqueue = [&](uint64_t at, int buf) -> hipError_t {
-    hipError_t e = hipMemcpyAsync(c->pin[buf], d_records.p + at, std::min(piece, total - at), hipMemcpyDeviceToHost, c->st);
-    return e != hipSuccess ? e : hipEventRecord(c->copied[buf], c->st);
+    hipError_t e = hipMemcpyAsync(s.pin[buf], d_records.p + at, std::min(piece, total - at), hipMemcpyDeviceToHost, c->st);
+    return e != hipSuccess ? e : hipEventRecord(s.copied[buf], c->st);
   };
   int cur = 0;
   if (total) HIPCHK(enqueue(0, 0));
   for (uint64_t at = 0; at < total && ok; at += piece, cur ^= 1) {
     if (at + piece < total) HIPCHK(enqueue(at + piece, cur ^ 1));
-    HIPCHK(hipEventSynchronize(c->copied[cur]));
+    HIPCHK(hipEventSynchronize(s.copied[cur]));
     const uint64_t len = std::min(piece, total - at);
-    ok = put(c->pin[cur], len);
+    ok = put(s.pin[cur], len);
   }
   if (total) HIPCHK(hipStreamSynchronize(c->st));
-  FILE* fh = f.h;
-  f.h = nullptr;
-  if (fclose(fh) != 0 && ok) {
+  if (fclose(f.take()) != 0 && ok) {
     io_errno = errno;
     ok = false;
   }

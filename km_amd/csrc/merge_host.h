@@ -1,66 +1,35 @@
 // merge_host.h — km_jf_file_info, km_counter_add_records, km_counter_add_jf, km_counter_merge_stats (host part of
 // kmgpu.hip; device side: merge_kernel.h; the piece arithmetic: merge_pieces.h)
 // ------------------------------------------------------------------ records of existing tables into a counter
-// A record area, of a file or packed from host arrays, goes through the counter's two pinned buffers into d_text in
-// pieces of whole records (the staging size rounded down to a multiple of the record size), each followed by
+// A record area, of a file or packed from host arrays, goes through the counter's staging (count_host.h) into d_text
+// in pieces of whole records (the staging size rounded down to a multiple of the record size), each followed by
 // k_count_add_records on the counter's stream: copy, event, kernel.  The host fills the next piece while the last
 // one runs; nothing waits except counter_reserve when it has to read the occupancy.
 namespace {
-int layout_failed(int rc, const std::string& err) {
-  return fail(rc == 1 ? KM_E_IO : rc == 2 ? KM_E_FORMAT : KM_E_K, "%s", err.c_str());
-}
-
-// The header of `path` as kmjf_open judges it; *f is left open, positioned anywhere.
-int merge_open(const char* path, jfio::Layout* lay, File* f) {
-  std::string err;
-  void* file = nullptr;
-  const int rc = jfio::read_layout(path, lay, &file, &err);
-  if (rc != 0) return layout_failed(rc, err);
-  f->h = static_cast<FILE*>(file);
-  if (lay->k < 2 || lay->k > 32) return fail(KM_E_K, "k=%d unsupported", lay->k);
-  return KM_OK;
-}
-
 // What every add_* checks first, in their order.
 int merge_check(const km_counter* c, int mode) {
   if (mode != KM_MERGE_SUM && mode != KM_MERGE_MAX) return fail(KM_E_ARG, "mode %d is neither KM_MERGE_SUM nor KM_MERGE_MAX", mode);
-  if (c->finished) return fail(KM_E_STATE, "counter already finished");
-  if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
-  return KM_OK;
+  return counter_usable(c);
 }
 
 // n records of kb + cb bytes; fill(dst, piece) writes piece.bytes bytes of them to a pinned buffer.
 template <typename Fill>
 int merge_enqueue(km_counter* c, uint64_t n, uint32_t kb, uint32_t cb, int mode, Fill fill) {
-  const uint64_t rec = (uint64_t)kb + cb, per = kmpiece::per_piece(c->stage, rec);
+  const uint64_t rec = (uint64_t)kb + cb, per = kmpiece::per_piece(c->stg.bytes, rec);
   HIPCHK(hipSetDevice(c->device));
-  // what add_bases / add_text left goes first; the bytes it would carry over are dropped (as km_counter_add_fastq)
-  KMCHK(counter_flush(c));
-  c->fill = 0;
-  c->own_from = 0;
+  KMCHK(counter_begin_pieces(c));
   const uint64_t pieces = kmpiece::n_pieces(n, per);
   for (uint64_t i = 0; i < pieces; ++i) {
     const kmpiece::Piece p = kmpiece::piece(n, per, rec, i);
-    HIPCHK(hipEventSynchronize(c->copied[c->cur]));
-    KMCHK(fill(c->pin[c->cur].h, p));
-    KMCHK(counter_reserve(c, p.records));               // every record a new key: the insert never meets a full table
-    HIPCHK(hipMemcpyAsync(c->d_text, c->pin[c->cur], p.bytes, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipEventRecord(c->copied[c->cur], c->st));
-    c->cur ^= 1;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (c->merge_timed) {
-      HIPCHK(hipEventCreate(&t0));
-      hipError_t e = hipEventCreate(&t1);
-      if (e != hipSuccess) { (void)hipEventDestroy(t0); return fail_hip(KM_E_HIP, "hipEventCreate", e); }
-      c->merge_spans.emplace_back(t0, t1);
-      HIPCHK(hipEventRecord(t0, c->st));
-    }
+    KMCHK(c->stg.claim());
+    KMCHK(fill(c->stg.mine, p));
+    KMCHK(counter_ship(c, p.bytes, p.records));         // every record a new key: the insert never meets a full table
+    KMCHK(c->merge_spans.open(c->st));
     hipLaunchKernelGGL(k_count_add_records, dim3(grid_for(p.records, 256)), dim3(256), 0, c->st, c->d_text.p, p.records,
                        kb, cb, mode, c->table.p, c->slots - 1, c->meta.p);
     HIPCHK(hipGetLastError());
-    if (c->merge_timed) HIPCHK(hipEventRecord(t1, c->st));
+    KMCHK(c->merge_spans.close(c->st));
   }
-  if (pieces) HIPCHK(hipEventSynchronize(c->copied[c->cur]));   // add_bases / add_text write pin[cur] without asking
   return KM_OK;
 }
 }  // namespace
@@ -70,7 +39,7 @@ extern "C" int km_jf_file_info(const char* path, int32_t* k, int32_t* canonical,
   if (!path) return fail(KM_E_ARG, "null argument");
   jfio::Layout lay;
   File f;
-  KMCHK(merge_open(path, &lay, &f));
+  KMCHK(open_layout(path, &lay, &f));
   if (k) *k = lay.k;
   if (canonical) *canonical = lay.canonical;
   if (n_records) *n_records = lay.n_records;
@@ -95,7 +64,7 @@ extern "C" int km_counter_add_jf(km_counter_t* c, const char* path, int mode, ui
   KMCHK(merge_check(c, mode));
   jfio::Layout lay;
   File f;
-  KMCHK(merge_open(path, &lay, &f));
+  KMCHK(open_layout(path, &lay, &f));
   if (lay.k != c->k || lay.canonical != c->canonical)
     return fail(KM_E_ARG, "%s holds k=%d canonical=%d, the counter k=%d canonical=%d", path, lay.k, lay.canonical, c->k,
                 c->canonical);
@@ -122,15 +91,9 @@ extern "C" int km_counter_merge_stats(km_counter_t* c, uint64_t* records_in, flo
   HIPCHK(hipSetDevice(c->device));
   unsigned long long m[CM_WORDS];
   KMCHK(counter_read_meta(c, m));
-  for (auto& s : c->merge_spans) {
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, s.first, s.second));
-    c->merge_kernel_ms += t;
-    (void)hipEventDestroy(s.first);
-    (void)hipEventDestroy(s.second);
-  }
-  c->merge_spans.clear();
+  float ms = 0.f;
+  KMCHK(c->merge_spans.drain(&ms));
   if (records_in) *records_in = m[CM_RECORDS];
-  if (kernel_ms) *kernel_ms = c->merge_kernel_ms;
+  if (kernel_ms) *kernel_ms = ms;
   return KM_OK;
 }

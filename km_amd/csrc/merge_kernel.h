@@ -55,6 +55,7 @@ __global__ __launch_bounds__(256) void k_count_add_records(const uint8_t* raw, u
                                                            unsigned long long* meta) {
   uint32_t claimed = 0, taken = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    // (k_unpack_records' decode, written out again: one function for both reorders the instructions of both kernels)
     uint64_t key = 0;
     uint32_t cnt = 0;
     if (kb == 8 && cb == 4) {                 // 12-byte records: three aligned dwords

@@ -19,6 +19,7 @@ from km_amd import count as kc
 from km_amd import lib as kmlib
 from oracle import jf_reader as jr
 from oracle import km_oracle as ko
+import test_count_quality as tq
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -398,6 +399,115 @@ def test_gpu_reads_and_records_on_one_counter(tmp_path):
     text_only = counted_model(first + third, 31)
     assert seen["kmers"] == int(text_only[1].sum(dtype=np.uint64)) and seen["distinct"] == want[0].size
     assert got[3]["records_in"] == counted_model(second, 31)[0].size
+
+
+@pytest.mark.gpu
+def test_gpu_every_producer_on_one_counter_at_the_smallest_staging(tmp_path, monkeypatch):
+    """Text, FASTQ and records take turns on one counter whose staging buffers have the smallest size there is
+    (256 bytes: no multiple of the 12-byte record), and the file leaves through the same two buffers.  Every call
+    is a segment of its own: no k-mer spans two calls or two kinds."""
+    monkeypatch.setenv("KM_COUNT_STAGE_BYTES", "256")
+    rng = np.random.default_rng(77)
+    q = ord("5")
+    reads = make_reads(77, 45)
+    fasta = b"".join(b">r%d\n%s\n" % (i, r) for i, r in enumerate(reads))
+    first = 3000                                                        # of the FASTA: what the calls before the last see
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    recs = [tq.record(b"q%d" % i, acgt[rng.integers(0, 4, 40)].tobytes(), tq.qualities(rng, 40).tobytes())
+            for i in range(80)]
+    fastq = b"".join(recs)
+    fq_first = len(b"".join(recs[:60])) + 17                            # ends inside record 60
+    bases = acgt[rng.integers(0, 4, 500)].tobytes()
+    text_models = [counted_model(reads, 31), tq.model_fastq(fastq, q, 31, True), tq.model(bases, 31, True)]
+    assert first + 100 < len(fasta) and max(len(r) for r in recs) < 256
+    assert not same(text_models[1], tq.model_fastq(fastq, 0, 31, True)) and text_models[1][0].size > 100
+    # records: keys the text has too, keys of their own, a fifth of them twice, some with count 0
+    keys = np.concatenate([text_models[0][0][:30], jr.canonical_np(random_keys(rng, 50, 31), 31)])
+    keys = np.concatenate([keys, keys[:20]])
+    counts = rng.integers(1, 1000, keys.size).astype(np.uint32)
+    counts[::9] = 0
+    jf_keys = np.concatenate([text_models[1][0][:25], jr.canonical_np(random_keys(rng, 75, 31), 31)])
+    jf_counts = rng.integers(1, 1000, jf_keys.size).astype(np.uint32)
+    jf_counts[::11] = 0
+    path = write_file(tmp_path / "in.jf", jf_keys, jf_counts, 31)
+    assert keys.size == 100 and jf_keys.size == 100 and keys.size * 12 > 4 * 256
+    want = merged_model(text_models + [(keys, counts), (jf_keys, jf_counts)], "sum")
+
+    c = kmlib.Counter(k=31, canonical=True)
+    try:
+        pos, tail, calls = 0, b"", 0
+        while pos < first:                                              # about a dozen pieces that overlap by k - 1
+            buf = tail + fasta[pos:min(pos + 700, first)]
+            pos += 700
+            used = c.add_text(buf, final=False)
+            tail, calls = buf[used:], calls + 1
+        assert calls == 5 and 0 < len(tail) < 200
+        used = c.add_fastq(fastq[:fq_first], final=False, min_qual_char=q)
+        assert used == fq_first - 17
+        c.add_records(keys, counts)
+        c.add_bases(bases)                                              # its end stays staged
+        assert c.add_jf(path) == 100
+        assert c.add_fastq(fastq[used:], final=True, min_qual_char=q) == len(fastq) - used
+        rest = tail + fasta[first:]
+        assert c.add_text(rest, final=True) == len(rest)
+        stats, merge = c.stats(), c.merge_stats()
+        c.finish().close()
+        got = c.records()
+        out = str(tmp_path / "out.jf")
+        c.write_jf(out)
+    finally:
+        c.close()
+    order = np.argsort(got[0], kind="stable")
+    assert same((got[0][order], got[1][order]), want)
+    assert stats["kmers"] == sum(int(m[1].sum(dtype=np.uint64)) for m in text_models)
+    assert stats["distinct"] == want[0].size
+    assert merge["records_in"] == int((counts > 0).sum()) + int((jf_counts > 0).sum())
+    rec = jr.read_jf(out)
+    order = np.argsort(rec["keys"], kind="stable")
+    assert (rec["k"], rec["canonical"]) == (31, True) and same((rec["keys"][order], rec["counts"][order]), want)
+    assert os.path.getsize(out) > 40 * 256                              # the file left in many pieces
+
+
+@pytest.mark.gpu
+def test_gpu_timed_runs_change_nothing_and_report_something(monkeypatch):
+    """KM_COUNT_TIME_FASTQ and KM_COUNT_TIME_MERGE put an event pair around every piece's kernels: the records stay
+    what they are, an untimed run reports 0, a timed one a time that only grows.  No bound on the times."""
+    monkeypatch.setenv("KM_COUNT_STAGE_BYTES", "4096")
+    rng = np.random.default_rng(78)
+    q = ord("+")
+    text, _ = tq.small_text()
+    keys = jr.canonical_np(random_keys(rng, 2000, 31), 31)
+    counts = rng.integers(0, 1000, keys.size).astype(np.uint32)
+    assert len(text) > 5 * 4096 and keys.size * 12 > 5 * 4096            # several spans each
+    want = merged_model([tq.small_want(q, 31, True)] * 2 + [(keys, counts)] * 2, "sum")
+    for time_fastq, time_merge in ((False, False), (True, False), (False, True), (True, True)):
+        monkeypatch.delenv("KM_COUNT_TIME_FASTQ", raising=False)
+        monkeypatch.delenv("KM_COUNT_TIME_MERGE", raising=False)
+        if time_fastq:
+            monkeypatch.setenv("KM_COUNT_TIME_FASTQ", "1")
+        if time_merge:
+            monkeypatch.setenv("KM_COUNT_TIME_MERGE", "1")
+        c = kmlib.Counter(k=31, canonical=True)
+        try:
+            seen = []
+            for _ in range(2):
+                assert c.add_fastq(text, final=True, min_qual_char=q) == len(text)
+                c.add_records(keys, counts)
+                seen.append((c.fastq_kernel_ms(), c.merge_stats()["kernel_ms"]))
+                assert (c.fastq_kernel_ms(), c.merge_stats()["kernel_ms"]) == seen[-1]   # no new piece: the same
+            c.finish().close()
+            assert c.fastq_kernel_ms() == seen[-1][0]                   # what was measured outlives the scratch
+            got = c.records()
+        finally:
+            c.close()
+        order = np.argsort(got[0], kind="stable")
+        assert same((got[0][order], got[1][order]), want), (time_fastq, time_merge)
+        for which, timed in ((0, time_fastq), (1, time_merge)):
+            first, second = seen[0][which], seen[1][which]
+            if timed:
+                assert np.isfinite(first) and np.isfinite(second) and 0 < first <= second, (which, seen)
+            else:
+                assert first == 0.0 and second == 0.0, (which, seen)
 
 
 @pytest.mark.gpu

@@ -677,9 +677,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
     wsb = smem;
     fwb = a.f_ws + (uint64_t)blockIdx.x * a.f_stride;
   }
-  const uint32_t cap = a.hs_cap;
+  // k = 32: the k-mer T^32 is the value EMPTY itself (no 64-bit value is free to mark an empty slot), so the hashed
+  // set cannot hold it.  It gets a slot of its own instead — ALL_T, the first of 64 slots kept out of the hashed
+  // range — whose state word alone says whether it is a node, on the stack or popped (0: never met).
+  const uint32_t cap_all = a.hs_cap;
+  const bool k32 = k == 32;
+  const uint32_t cap = k32 ? cap_all - 64u : cap_all;
+  const uint32_t ALL_T = cap;
   uint64_t* keys = reinterpret_cast<uint64_t*>(wsb);
-  uint64_t* words = keys + cap;
+  uint64_t* words = keys + cap_all;
   BranchFrame* bf = reinterpret_cast<BranchFrame*>(words + a.words_cap);
   uint16_t* state = reinterpret_cast<uint16_t*>(bf + a.bcap);
   // The target's own k-mers are NOT entered into the node set: a table of POSITIONS hashed by (k-1)-mer prefix,
@@ -690,7 +696,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
   // those k-mers were three quarters of a wave's LDS.
   using pos_t = typename std::conditional<BIG, uint32_t, uint16_t>::type;
   constexpr uint32_t POS_NONE = (uint32_t)(pos_t)~(pos_t)0, NO_NODE = 0xFFFFFFFFu;
-  pos_t* pos = reinterpret_cast<pos_t*>(state + cap);
+  pos_t* pos = reinterpret_cast<pos_t*>(state + cap_all);
   const uint32_t pcap = a.pcap;
   // its hash looks at the low 32 bits of the prefix only (the last 16 bases: one multiply, and the set-up reads them
   // straight off the packed target with 32-bit operations); pcap is a power of two
@@ -735,15 +741,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
   __syncthreads();                                           // the packed words
   if (a.stamps) lifeB = __builtin_amdgcn_s_memrealtime();
   if constexpr (BIG) {
-    for (uint32_t s = lane; s < cap; s += 64) { keys[s] = EMPTY; state[s] = 0; }
+    for (uint32_t s = lane; s < cap_all; s += 64) { keys[s] = EMPTY; state[s] = 0; }
     for (uint32_t s = lane; s < pcap; s += 64) pos[s] = (pos_t)POS_NONE;
   } else {
     // LDS: 16 bytes per store (cap and pcap are multiples of 64: whole uint4s in all three arrays)
     const uint4 ones = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
     uint4* kq = reinterpret_cast<uint4*>(keys);
-    for (uint32_t s = lane; s < cap / 2; s += 64) kq[s] = ones;
+    for (uint32_t s = lane; s < cap_all / 2; s += 64) kq[s] = ones;
     uint4* sq = reinterpret_cast<uint4*>(state);
-    for (uint32_t s = lane; s < cap / 8; s += 64) sq[s] = make_uint4(0u, 0u, 0u, 0u);
+    for (uint32_t s = lane; s < cap_all / 8; s += 64) sq[s] = make_uint4(0u, 0u, 0u, 0u);
     uint4* pq = reinterpret_cast<uint4*>(pos);
     for (uint32_t s = lane; s < pcap / 8; s += 64) pq[s] = ones;
   }
@@ -772,6 +778,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
     const uint32_t p_ = (uint32_t)pos[pos_home((uint32_t)(y >> 2))];
     const bool some = p_ != POS_NONE;
     return (kmer_at(some ? p_ : 0u) == y && some) ? p_ : NO_NODE;
+  };
+  // the node set with T^32 in its own slot (see ALL_T above): wave-cooperative lookup, per-lane lookup, per-lane insert
+  auto node_find = [&](uint64_t y, bool* found) -> int {
+    if (k32 && y == EMPTY) { *found = state[ALL_T] != 0; return (int)ALL_T; }
+    return set_find<2>(keys, cap, y, found);
+  };
+  auto node_lookup_lane = [&](uint64_t y, bool* found) -> int {
+    if (k32 && y == EMPTY) { *found = state[ALL_T] != 0; return (int)ALL_T; }
+    return set_lookup_lane<2>(keys, cap, y, found);
+  };
+  auto node_insert_lane = [&](uint64_t y, bool* was_new) -> int {
+    if (k32 && y == EMPTY) { *was_new = state[ALL_T] == 0; return (int)ALL_T; }
+    return set_insert_lane<2>(keys, cap, y, was_new);
   };
   // y is probably a node (a target k-mer, or a k-mer sitting in its home slot of the node set): a hint
   auto node_hint = [&](uint64_t y) -> bool { return ref_index(y) != NO_NODE || keys[set_home(y >> 2, cap)] == y; };
@@ -831,8 +850,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
         const uint64_t xw = kmer_at((uint32_t)pos[pos_home((uint32_t)(kk >> 2))]);   // (the slot was written: by this k-mer, if by no other)
         if (xw == kk) dup = 1;
         else if ((xw >> 2) == (kk >> 2)) shared = 1;
+        if (k32 && kk == EMPTY) {
+          // T^32 (see ALL_T): the second half of its state word tells a twin in another lane that it came second;
+          // who shares its prefix is not looked for: such a target is not the epilogue's
+          shared = 1;
+          if (!dup) {
+            const uint32_t old = atomicOr(reinterpret_cast<uint32_t*>(state + ALL_T), 0x10000u);
+            if (old & 0x10000u) dup = 1;
+            else state[ALL_T] = slot_meta(ST_NODE, i);
+          }
+        }
         uint32_t sl = set_home(kk >> 2, cap);
-        for (uint32_t step = 0; step < cap && !dup; ++step) {
+        for (uint32_t step = 0; step < cap && !dup && !(k32 && kk == EMPTY); ++step) {
           const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&keys[sl]), (unsigned long long)EMPTY,
                                                    (unsigned long long)kk);
           if (old == EMPTY) { state[sl] = slot_meta(ST_NODE, i); break; }
@@ -1196,7 +1225,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
                 if (ref_index(rkey) != NO_NODE) {            // a k-mer of the target: a node
                   found = true; st8 = ST_NODE; slot = 0;
                 } else {
-                  slot = set_lookup_lane<2>(keys, cap, rkey, &found);
+                  slot = node_lookup_lane(rkey, &found);
                   if (found) st8 = meta_state(state[slot]);
                 }
               }
@@ -1214,7 +1243,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
               bool fresh = false;
               if (lane < f) {
                 if (!found) {
-                  slot = set_insert_lane<2>(keys, cap, rkey, &fresh);
+                  slot = node_insert_lane(rkey, &fresh);
                 }
                 if (slot >= 0) {
                   state[slot] = slot_meta(ST_ONSTACK, 0);
@@ -1281,7 +1310,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
           if (__builtin_amdgcn_readfirstlane((int)(ref_index(child) != NO_NODE))) {   // a k-mer of the target: a node
             found = true; stt = ST_NODE;
           } else {
-            slot = set_find<2>(keys, cap, child, &found);
+            slot = node_find(child, &found);
             if (slot < 0) { st = BIG ? T_INTERNAL : T_NEEDS_BIG; break; }
             stt = found ? meta_state(state[slot]) : 0u;
           }
@@ -1323,18 +1352,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
             if (!found && set_count + 1 > set_limit) {
               // drop the POPPED tombstones: rebuild the set from nodes + live stack
               __syncthreads();
-              for (uint32_t s = lane; s < cap; s += 64) { keys[s] = EMPTY; state[s] = 0; }
+              for (uint32_t s = lane; s < cap_all; s += 64) { keys[s] = EMPTY; state[s] = 0; }
               __syncthreads();
               bool wn;
               for (uint32_t j = lane; j < n_nodes; j += 64) {
                 const uint64_t kk = (j < n_ref) ? kmer_at(j) : a.node_kmer[nb + j];
                 if (j < n_ref && (uint32_t)pos[pos_home((uint32_t)(kk >> 2))] == j) continue;   // it owns its slot of the position table
-                const int s2 = set_insert_lane<2>(keys, cap, kk, &wn);
+                const int s2 = node_insert_lane(kk, &wn);
                 if (s2 >= 0) state[s2] = slot_meta(ST_NODE, j);
               }
               __syncthreads();
               for (uint32_t j = 1 + lane; j < depth; j += 64) {       // (frame 0 is the seed: a node)
-                const int s2 = set_insert_lane<2>(keys, cap, fk[j], &wn);
+                const int s2 = node_insert_lane(fk[j], &wn);
                 if (s2 >= 0) {
                   if (wn) state[s2] = slot_meta(ST_ONSTACK, 0);
                   fs[j] = (uint32_t)s2;
@@ -1343,7 +1372,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
               __syncthreads();
               set_count = n_losers + (n_nodes - n_ref) + (depth - reg);
               if (set_count + 1 > set_limit) { st = BIG ? T_INTERNAL : T_NEEDS_BIG; break; }
-              slot = set_find<2>(keys, cap, child, &found);
+              slot = node_find(child, &found);
               if (slot < 0 || found) { st = T_INTERNAL; break; }
             }
             if (depth >= a.fcap) { st = BIG ? T_INTERNAL : T_NEEDS_BIG; break; }   // fast tier: bounded frames
@@ -1409,7 +1438,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
   bool answered = false;
   if constexpr (!BIG) {
     const uint32_t m = n_nodes, n_walk = n_nodes - n_ref;
-    if (a.epi != nullptr && ref_pure && st == T_OK && n_ref >= 2 && n_walk <= 64u * EPI_CHUNKS && m < 0x3FFFu) {
+    // (T^32 as a node is outside the hashed set the epilogue reads prefixes from: such a target is k_graph's)
+    if (a.epi != nullptr && ref_pure && st == T_OK && n_ref >= 2 && n_walk <= 64u * EPI_CHUNKS && m < 0x3FFFu &&
+        !(k32 && state[ALL_T] != 0)) {
       constexpr uint32_t NONE = 0xFFFFFFFFu;
       constexpr uint32_t REF_REGS = 8;                     // reference counts a lane keeps (targets of up to 512 k-mers)
       // the nodes whose k-mer has the (k-1)-mer prefix P, the node `self` aside: how many, and one of

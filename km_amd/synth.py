@@ -536,3 +536,127 @@ def crossover_sweep(k, margins=CROSSOVER_MARGINS, extra_ins=0, seed=0, solo=(), 
     cases = [crossover_case(pool, "x%d_%+d" % (k, v), length, 99 * k - v, extra_ins) for v in margins]
     cases += [crossover_case(pool, "solo%d_%+d" % (k, v), length, 99 * k - v, snvs=False) for v in solo]
     return cases + ([nested_case(pool, "nested%d" % k)] if nested else [])
+
+
+# ---------------------------------------------------------------------------- structured cases
+# Low-complexity and small-k inputs (tests/test_structured_kmers.py, tests/test_oracle_c.py): homopolymers,
+# microsatellites, palindromes, a k-mer next to its own reverse complement, tables that hold the whole key space.
+# Unlike the crossover cases above these WANT the coincidences that random 31-mers never show.
+def random_seq(rng, n):
+    return "".join("ACGT"[i] for i in rng.integers(0, 4, n))
+
+
+def has_repeated_kmer(seq, k):
+    mers = _kmers_of(seq, k)
+    return len(set(mers)) != len(mers)
+
+
+def unique_kmer_seq(rng, n, k):
+    """A random sequence of n bases with no k-mer twice."""
+    while True:
+        s = random_seq(rng, n)
+        if not has_repeated_kmer(s, k):
+            return s
+
+
+def reads_to_records(reads, k, canonical=True):
+    """records_from_reads, also for a table that stores k-mers as they are read."""
+    if canonical:
+        return records_from_reads(reads, k)
+    acc = {}
+    for seq, c in reads:
+        for key in km.sliding_kmers(km.encode(seq), k).tolist():
+            acc[key] = acc.get(key, 0) + c
+    keys = np.array(sorted(acc), dtype=np.uint64)
+    return keys, np.array([acc[x] for x in keys.tolist()], dtype=np.uint32)
+
+
+def end_duplication_case(k, seed=0):
+    """A tandem duplication that reaches the target's end: the variant path is the whole reference path plus a
+    junction and a second copy of the tail, so the reference path is a proper prefix of it."""
+    rng = np.random.default_rng(8100 + 37 * k + seed)
+    T = unique_kmer_seq(rng, 3 * k + 10, k)
+    return {"name": "enddup%d" % k, "target": T, "reads": [(T, 60), (T + T[-(k + 5):], 30)], "k": k}
+
+
+def dense_counts(rng, n):
+    """30 % in 100 .. 70 000 (both sides of the 16-bit escape), the rest in 1 .. 5 (around `count`)."""
+    c = rng.integers(1, 6, size=n)
+    big = rng.random(n) < 0.3
+    c[big] = rng.integers(100, 70_001, size=int(big.sum()))
+    return c.astype(np.uint32)
+
+
+def small_k_case(k, canonical, seed=0, n_targets=12):
+    """k <= 10.  k <= 7: a table over the whole key space (k <= 4) or a seeded 80 % of it; random targets with no
+    repeated k-mer.  k = 8 .. 10 (a half-full table of that size hardly branches): the targets' own reads plus a
+    substitution or an insertion each, and a quarter of the key space around them at counts of 1 .. 5."""
+    rng = np.random.default_rng(500 + k + 1000 * seed + (0 if canonical else 7919))
+    space = np.arange(1 << (2 * k), dtype=np.uint64)
+    if canonical:
+        space = space[space <= km.revcomp(space, k)]
+    max_len = min((1 << (2 * k)) // 2 + k, 60)
+    targets = [unique_kmer_seq(rng, int(rng.integers(k + 1, max_len)), k) for _ in range(n_targets)]
+    if k <= 7:
+        keys = space if k <= 4 else space[rng.random(space.size) < 0.8]
+        counts = dense_counts(rng, keys.size)
+    else:
+        reads = []
+        for i, T in enumerate(targets):
+            reads.append((T, int(rng.integers(40, 70_000 if i % 4 == 0 else 200))))
+            p = int(rng.integers(1, len(T) - 1))
+            if i % 2:
+                var = T[:p] + "ACGT"[("ACGT".index(T[p]) + 1 + i % 3) % 4] + T[p + 1:]
+            else:
+                var = T[:p] + random_seq(rng, 1 + i % 5) + T[p:]
+            reads.append((var, max(1, reads[-1][1] // 2)))
+        rk, rc = reads_to_records(reads, k, canonical)
+        pad = space[rng.random(space.size) < 0.25]
+        pad = pad[~np.isin(pad, rk)]
+        keys = np.concatenate([rk, pad])
+        counts = np.concatenate([rc, rng.integers(1, 6, size=pad.size).astype(np.uint32)])
+        order = np.argsort(keys)
+        keys, counts = keys[order], counts[order]
+    return {"k": k, "canonical": canonical, "keys": keys, "counts": counts, "targets": targets,
+            "names": ["k%d_%d" % (k, i) for i in range(n_targets)]}
+
+
+REPEAT_UNITS = ("A", "T", "AT", "TA", "AC", "CG")
+
+
+def repeat_case(k, unit, seed=0):
+    """Reads that enter a repeat of `unit` from the target and never leave it (the walk circles the repeat)."""
+    rng = np.random.default_rng(8200 + 41 * k + 7 * REPEAT_UNITS.index(unit) + seed)
+    while True:
+        T = random_seq(rng, k + 5) + unit * (6 // len(unit)) + random_seq(rng, k + 7)
+        if not has_repeated_kmer(T, k):
+            break
+    cut = k + 5 + 6
+    return {"name": "rep_%s_%d" % (unit, k), "target": T, "k": k,
+            "reads": [(T, 50), (T[:cut] + unit * (k + 4), 30)]}
+
+
+def inversion_case(k, seed=0):
+    """Target A + B + C, reads with B inverted: the walk follows the reverse strand of B, and where the table is
+    canonical it meets every k-mer of B again as its own reverse complement."""
+    rng = np.random.default_rng(8300 + 43 * k + seed)
+    T = unique_kmer_seq(rng, (k + 10) + (2 * k + 3) + (k + 10), k)
+    a, b = k + 10, k + 10 + 2 * k + 3
+    return {"name": "inv%d" % k, "target": T, "k": k,
+            "reads": [(T, 60), (T[:a] + revcomp_str(T[a:b]) + T[b:], 30)]}
+
+
+def hairpin_case(k, seed=0):
+    """Target S + rc(S): every k-mer stands next to its reverse complement; for even k the centre one is both."""
+    rng = np.random.default_rng(8400 + 47 * k + seed)
+    while True:
+        S = random_seq(rng, k + 9)
+        T = S + revcomp_str(S)
+        if not has_repeated_kmer(T, k):
+            return {"name": "hairpin%d" % k, "target": T, "k": k, "reads": [(T, 50)]}
+
+
+def structured_cases(k, seed=0):
+    """Every structured walk case at one k, each with a table of its own."""
+    return ([repeat_case(k, u, seed) for u in REPEAT_UNITS]
+            + [inversion_case(k, seed), hairpin_case(k, seed), end_duplication_case(k, seed)])

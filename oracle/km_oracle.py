@@ -26,7 +26,10 @@ so node numbering, the order of alternative paths and therefore the
 fixes one admissible order: reference k-mers are registered and extended in
 target order (node i == i-th k-mer of the target), walk-discovered nodes follow
 in registration order, and alternative paths are sorted by their node-index
-tuple.  Everything else follows the reference statement by statement.
+tuple WITHOUT the two capping nodes: lexicographic, so a path that is a proper
+prefix of another comes first (oracle/km_oracle.c: path_cmp and
+deliver_kernel.h: rle_less order them the same way).  Everything else follows
+the reference statement by statement.
 
 PARITY PIN.  Checked in tests/test_oracle_golden.py against golden vectors
 produced by the unmodified reference (tests/golden/make_golden.py): exact TSV
@@ -210,7 +213,7 @@ def enumerate_paths(edges, before, after, source, sink):
         if left[-1] != source or right[-1] != sink:
             continue
         found.add(tuple(reversed(left)) + tuple(right))
-    return sorted(found)                       # canonical order (see header)
+    return found                               # a set: graph_paths gives it its order
 
 
 def graph_paths(kmers, n_ref, stats=None):
@@ -229,7 +232,9 @@ def graph_paths(kmers, n_ref, stats=None):
     if stats is not None:
         stats["removed_ref_edges"] = removed
         stats["nonref_edges"] = len(edges)
-    return [p[1:-1] for p in enumerate_paths(edges, before, after, n - 2, n - 1)]
+    # canonical order (see header): sorted AFTER the caps are stripped — with the sink attached, whose index is
+    # larger than every node's, a path that is a proper prefix of another would sort after it
+    return sorted(p[1:-1] for p in enumerate_paths(edges, before, after, n - 2, n - 1))
 
 
 # ----------------------------------------------------------------------- naming

@@ -67,3 +67,57 @@ def test_c_oracle_statuses():
     assert hit > 0
     assert co.analyse(np.zeros(32, np.uint8))["status"] == 2        # poly-A: repeated k-mer
     assert co.analyse(np.zeros(10, np.uint8))["status"] == 3        # shorter than k
+
+
+# ------------------------------------------------------------------ one path order
+def _both(keys, counts, k, canonical, seq, name="t"):
+    co = c_oracle.COracle(keys, counts, k, canonical)
+    py = ko.KmerDB(None, 0.05, 5, records={"k": k, "canonical": canonical, "keys": keys, "counts": counts})
+    c = co.analyse(km.encode(seq))
+    p = ko.analyse_target(seq, name, py)
+    _same(c, p, k)
+    return c, p
+
+
+def _prefix_pairs(paths):
+    """Pairs (i, j) of paths of which the first is a proper prefix of the second."""
+    return [(i, j) for i, a in enumerate(paths) for j, b in enumerate(paths)
+            if len(a) < len(b) and list(b[:len(a)]) == list(a)]
+
+
+@pytest.mark.parametrize("k", [11, 21, 31, 32])
+def test_duplication_reaching_the_targets_end_puts_the_prefix_path_first(k):
+    """A tandem duplication that reaches the target's end: the reference path is a proper prefix of the variant's.
+    Both oracles sort paths without the caps, so the reference path comes first."""
+    case = synth.end_duplication_case(k)
+    keys, counts = synth.records_from_reads(case["reads"], k)
+    c, p = _both(keys, counts, k, True, case["target"], case["name"])
+    n_ref = len(case["target"]) - k + 1
+    ref = list(range(n_ref))
+    assert c["paths"][0] == ref and len(c["paths"]) == 2
+    assert [len(x) for x in c["paths"]] == [n_ref, n_ref + k + 5] and c["min_cov"] == [90, 30]
+    assert c["paths"][1][:n_ref] == ref                              # ... + junction + second copy of the tail
+    assert _prefix_pairs(c["paths"]) == [(0, 1)]
+    rows = ko.target_rows(p, "mem.jf")
+    assert sorted(r.split("\t")[2] for r in rows) == ["ITD", "ITD", "Reference"]
+
+
+@pytest.mark.parametrize("canonical", [True, False])
+@pytest.mark.parametrize("k", [2, 3, 4, 5, 6, 7])
+def test_c_oracle_on_dense_small_k_tables(k, canonical):
+    """Tables over the whole key space (or half of it): every walk branches, loops and meets reverse complements,
+    and paths that are a prefix of another are common.  Nodes, counts, probes, paths IN ORDER, min coverages."""
+    n_prefix = n_multi = 0
+    for seed in (0, 1):
+        case = synth.small_k_case(k, canonical, seed)
+        co = c_oracle.COracle(case["keys"], case["counts"], k, canonical)
+        py = ko.KmerDB(None, 0.05, 5, records={"k": k, "canonical": canonical, "keys": case["keys"],
+                                               "counts": case["counts"]})
+        for name, seq in zip(case["names"], case["targets"]):
+            c = co.analyse(km.encode(seq))
+            _same(c, ko.analyse_target(seq, name, py), k)
+            assert c["paths"] == sorted(c["paths"])
+            n_prefix += bool(_prefix_pairs(c["paths"]))
+            n_multi += len(c["paths"]) > 1
+    assert n_multi >= 6, n_multi
+    assert n_prefix >= 1, n_prefix                                   # (the test does not go vacuous)

@@ -500,6 +500,55 @@ int km_counter_add_jf(km_counter_t* c, const char* path, int mode, uint64_t* n_r
  * their kernels by HIP events on the counter's stream, 0 otherwise.  Either may be NULL. */
 int km_counter_merge_stats(km_counter_t* c, uint64_t* records_in, float* kernel_ms);
 
+/* ---- histogram of counts and table statistics -----------------------------------------------------
+ * What `jellyfish histo` and `jellyfish stats` print, from counts that are already in HBM or from a file streamed
+ * through it ("Histogram and statistics").  Both definitions are THIS PROJECT'S READING of the two
+ * Jellyfish commands, not checked against a run of Jellyfish.
+ * Keys looked at: a record or slot with count c takes part iff max(lower_count, 1) <= c <= upper_count (a count of 0
+ * is not a key); bins and statistics see exactly those.
+ * Bins, with 64-bit low <= high and increment >= 1:
+ *   base   = low > 1 ? (increment >= low ? 1 : low - increment) : 1
+ *   ceil   = high + increment
+ *   n_bins = (ceil + increment - base) / increment                 (integer division)
+ *   bin(c) = c < base ? 0 : c > ceil ? n_bins - 1 : (c - base) / increment
+ * bin i is labelled base + i * increment; the defaults (1, 10000, 1) give 10 001 bins, the last one labelled 10001
+ * and holding every count of 10 001 and above.
+ * Statistics: unique = keys with count 1, distinct = keys, total = the 64-bit sum of their counts, max_count = the
+ * largest count (0 if no key). */
+typedef struct { uint64_t unique, distinct, total, max_count, reserved[2]; } km_histo_stats_t;
+
+/* host only: the bin layout of (low, high, increment); either output may be NULL.  KM_E_ARG, km_last_error naming the
+ * value, for increment == 0, low > high, high + 2 * increment beyond 64 bits, more than 2^24 bins. */
+int km_histo_layout(uint64_t low, uint64_t high, uint64_t increment, uint64_t* base, uint64_t* n_bins);
+/* A counter BEFORE finish (the counting table: everything added so far, waits for it, changes nothing the table
+ * holds — the counter takes further add_* and finish afterwards) or AFTER finish (the kept records).  Before finish the
+ * call enqueues what is staged, as km_counter_stats does: the pieces end where they would not have without the call,
+ * so km_counter_stats_t.slots and n_grow (WHEN the table doubles) may differ from those of a counter never asked;
+ * bases, kmers, distinct, the finished database and the records do not.  bins[cap] receives
+ * n_bins values, KM_E_CAPACITY if cap is smaller; bins or stats may be NULL.  Before any device work: KM_E_ARG as
+ * km_histo_layout, KM_E_CAPACITY; a sticky FASTQ format error as every call on the counter returns it. */
+int km_counter_histo(km_counter_t* c, uint64_t low, uint64_t high, uint64_t increment, uint32_t lower_count,
+                     uint32_t upper_count, uint64_t* bins, uint64_t cap, km_histo_stats_t* stats);
+/* The record area of a binary/sorted file, read with pread into pinned staging piece by piece (whole records);
+ * the file is never in host memory or HBM as a whole.  No counter is needed.  *k, *n_records (may be NULL): from the
+ * header.  Before any device work: KM_E_ARG, KM_E_IO / KM_E_FORMAT / KM_E_K as kmjf_open gives them, KM_E_CAPACITY.
+ * A file without records returns zeros without a launch.  stream: a hipStream_t, NULL = one of the library's own. */
+int km_jf_histo(int device, const char* path, uint64_t low, uint64_t high, uint64_t increment, uint32_t lower_count,
+                uint32_t upper_count, uint64_t* bins, uint64_t cap, km_histo_stats_t* stats, int32_t* k,
+                uint64_t* n_records, void* stream);
+/* Environment, read by the two calls above: KM_HISTO_ROUNDS = how many rounds a wave spends adding the lanes that hold
+ * one bin as a single LDS atomic before the rest add on their own (0..64; the results are the same at any value; for
+ * tests and measurement, the default is the measured choice of DESIGN.md 10); KM_COUNT_STAGE_BYTES sizes the pinned
+ * buffers of km_jf_histo as it sizes a counter's. */
+/* the time of the histogram kernels of the calling thread's last km_counter_histo / km_jf_histo, by HIP events */
+int km_histo_kernel_ms(float* ms);
+/* Host only, the text of the two commands.  km_histo_text: one line "<label> <n>\n" per bin with n > 0, or per bin
+ * with full != 0; km_histo_stats_text: "Unique:    <n>\nDistinct:  <n>\nTotal:     <n>\nMax_count: <n>\n".
+ * out == NULL asks for *len only; KM_E_CAPACITY if cap < *len (nothing is written). */
+int km_histo_text(uint64_t base, uint64_t increment, const uint64_t* bins, uint64_t n_bins, int full, char* out,
+                  uint64_t cap, uint64_t* len);
+int km_histo_stats_text(const km_histo_stats_t* stats, char* out, uint64_t cap, uint64_t* len);
+
 /* ---- measurement helpers (bench.py at N = 1 holds no device buffers of its own) ------------- */
 int km_device_sync(int device);                                    /* hipDeviceSynchronize on `device`          */
 /* device-to-device copy of `bytes` bytes, `reps` times: read + write GB/s (the box's large-copy

@@ -1,4 +1,5 @@
-"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, ``count`` and ``merge``.
+"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, ``count``, ``merge``, ``histo``
+and ``stats``.
 
 Same flags, same ``#key:value`` echo, same TSV and ``#Elapsed time`` trailer as
 km/tools/find_mutation.py:17-60 and km/argparser/find_mutation.py:4-58, so the
@@ -311,6 +312,8 @@ def main_count(args, err=None):
             counter.write_jf(args.output, cmdline=cmdline)
         else:
             keys, counts = counter.records()
+        if args.histo:
+            kc.write_histo(counter, args.histo)
     finally:
         counter.close()
         db.close()
@@ -339,6 +342,8 @@ def main_merge(args, err=None):
             counter.write_jf(args.output, cmdline=cmdline)
         else:
             keys, counts = counter.records()
+        if args.histo:
+            kc.write_histo(counter, args.histo)
     finally:
         counter.close()
         db.close()
@@ -347,6 +352,51 @@ def main_merge(args, err=None):
     err.write("#mode:%s\n" % mode)
     if not args.jellyfish_order:
         kc.write_records(args.output, keys, counts, stats["k"], stats["canonical"], cmdline=cmdline)
+
+
+def _write_text(text, path, out=None):
+    if path:
+        with open(path, "w") as fh:
+            fh.write(text)
+    else:
+        out = sys.stdout if out is None else out
+        out.write(text)
+        out.flush()
+
+
+def main_histo(args, out=None):
+    """`jellyfish histo -l LOW -h HIGH -i INC [-f] db.jf` on the GPU (km_amd.count.histo_file): one line
+    "<count> <k-mers>" per bin; counts above HIGH + INC collect in the last bin.  -L / -U look only at the records
+    with -L <= count <= -U.  This project's reading of the command, not checked against a run of Jellyfish."""
+    from . import count as kc
+    base, bins, _ = kc.histo_file(args.db, low=args.low, high=args.high, increment=args.increment,
+                                  lower_count=args.lower_count, upper_count=args.upper_count, device=default_device())
+    _write_text(kc.format_histo(base, args.increment, bins, full=args.full), args.output, out)
+
+
+def main_stats(args, out=None):
+    """`jellyfish stats [-L N] [-U N] db.jf` on the GPU: Unique (count 1), Distinct, Total (sum of counts) and
+    Max_count of the records with -L <= count <= -U.  This project's reading, not checked against Jellyfish."""
+    from . import count as kc
+    _, _, stats = kc.histo_file(args.db, lower_count=args.lower_count, upper_count=args.upper_count,
+                                device=default_device())
+    _write_text(kc.format_stats(stats), args.output, out)
+
+
+def _count_value(text):
+    """argparse type of the count-valued options of histo / stats: a non-negative integer."""
+    value = int(text)
+    if value < 0:
+        raise argparse.ArgumentTypeError("expected a non-negative integer, got %r" % text)
+    return value
+
+
+def _count32(text):
+    """argparse type of -L / -U of histo / stats: a count, 0 .. 2^32 - 1."""
+    value = _count_value(text)
+    if value > 0xFFFFFFFF:
+        raise argparse.ArgumentTypeError("counts are 32-bit: at most 4294967295, got %r" % text)
+    return value
 
 
 def _one_char(text):
@@ -387,6 +437,8 @@ def build_parser():
     ct.add_argument("-Q", "--min-qual-char", type=_one_char, default=None, metavar="CHAR",
                     help="a base of a FASTQ read whose quality character is below CHAR is read as N (FASTQ is then "
                          "parsed on the GPU; no effect on FASTA)")
+    ct.add_argument("--histo", metavar="FILE", default=None,
+                    help="also write the histogram of the counts written (after -L), as `histo OUT` prints it")
     ct.add_argument("reads", nargs="+", help="FASTA or FASTQ files, plain or gzip; - is stdin")
     mg = sub.add_parser("merge", help="sum (or --max) the counts of several .jf files of one k on the GPU -> one .jf")
     mg.add_argument("-L", "--lower-count", type=int, default=1, help="don't output k-mers with a merged count < lower-count")
@@ -394,7 +446,26 @@ def build_parser():
     mg.add_argument("-o", "--output", default="mer_counts_merged.jf", help="output file (default: mer_counts_merged.jf)")
     mg.add_argument("--jellyfish-order", action="store_true",
                     help="write the records in Jellyfish's own order (matrix position, then key), sorted on the GPU")
+    mg.add_argument("--histo", metavar="FILE", default=None,
+                    help="also write the histogram of the counts written (after -L), as `histo OUT` prints it")
     mg.add_argument("inputs", nargs="+", metavar="db.jf", help="binary/sorted files of one k and one canonical setting")
+    hs = sub.add_parser("histo", add_help=False,
+                        help="histogram of the counts of a .jf file, on the GPU (-h is --high as in Jellyfish: help is "
+                             "--help only)")
+    hs.add_argument("--help", action="help", help="show this help message and exit (-h is --high, as in Jellyfish)")
+    hs.add_argument("-l", "--low", type=_count_value, default=1, help="low count value of the histogram (default: -l 1)")
+    hs.add_argument("-h", "--high", type=_count_value, default=10000, help="high count value of the histogram (default: -h 10000)")
+    hs.add_argument("-i", "--increment", type=_count_value, default=1, help="width of a bin (default: -i 1)")
+    hs.add_argument("-f", "--full", action="store_true", help="print every bin, the empty ones too")
+    hs.add_argument("-L", "--lower-count", type=_count32, default=1, help="ignore k-mers with count < lower-count")
+    hs.add_argument("-U", "--upper-count", type=_count32, default=0xFFFFFFFF, help="ignore k-mers with count > upper-count")
+    hs.add_argument("-o", "--output", default=None, help="output file (default: standard output)")
+    hs.add_argument("db", metavar="db.jf", help="a binary/sorted file")
+    ss = sub.add_parser("stats", help="Unique / Distinct / Total / Max_count of a .jf file, on the GPU")
+    ss.add_argument("-L", "--lower-count", type=_count32, default=1, help="ignore k-mers with count < lower-count")
+    ss.add_argument("-U", "--upper-count", type=_count32, default=0xFFFFFFFF, help="ignore k-mers with count > upper-count")
+    ss.add_argument("-o", "--output", default=None, help="output file (default: standard output)")
+    ss.add_argument("db", metavar="db.jf", help="a binary/sorted file")
     return parser
 
 
@@ -421,6 +492,10 @@ def main(argv=None):
         main_count(args)
     elif cmd == "merge":
         main_merge(args)
+    elif cmd == "histo":
+        main_histo(args)
+    elif cmd == "stats":
+        main_stats(args)
     else:
         parser.print_help(sys.stderr)
         sys.exit(1)

@@ -7,8 +7,9 @@ front of every km tool (``python -m km_amd count``).
 ``count_files`` streams FASTA / FASTQ files (plain or gzip) through :class:`km_amd.lib.Counter` and returns the
 database built on the device from the counted records; ``write_records`` writes such records in the file
 framing the readers of this project load, sorted by key; ``write_jellyfish`` writes them in Jellyfish's own
-record order (sorted on the GPU), as ``Counter.write_jf`` does for records still on the device.  Only the
-standard library and numpy.
+record order (sorted on the GPU), as ``Counter.write_jf`` does for records still on the device.
+``histo_file``, ``format_histo`` and ``format_stats`` are behind ``python -m km_amd histo`` / ``stats``: the histogram
+of a file's counts and its four statistics in one pass on the GPU.  Only the standard library and numpy.
 """
 
 import gzip
@@ -126,6 +127,34 @@ def merge_files(paths, mode="sum", lower_count=1, device=0, expected_distinct=0,
         return db, stats, counter
     counter.close()
     return db, stats
+
+
+def histo_file(path, low=1, high=10000, increment=1, lower_count=1, upper_count=0xFFFFFFFF, device=0):
+    """The histogram of the counts of a `binary/sorted` file and its four statistics, what `jellyfish histo -l low
+    -h high -i increment` and `jellyfish stats` print -> (base, bins ndarray uint64, stats dict), as Counter.histo.
+    The records stream through the GPU piece by piece (lib.jf_histo); a record takes part iff
+    max(lower_count, 1) <= count <= upper_count.  This project's reading of the two commands, not checked against a
+    run of Jellyfish."""
+    return _lib.jf_histo(path, low=low, high=high, increment=increment, lower_count=lower_count,
+                         upper_count=upper_count, device=device)
+
+
+def format_histo(base, increment, bins, full=False):
+    """The text of `histo`: one line "<label> <n>" per bin with n > 0, or per bin with full (the native writer)."""
+    return _lib.histo_text(base, increment, bins, full=full)
+
+
+def format_stats(stats):
+    """The text of `stats`: Unique / Distinct / Total / Max_count, labels padded to one column (the native writer)."""
+    return _lib.histo_stats_text(stats)
+
+
+def write_histo(counter, path):
+    """The default-layout histogram of a finished counter's records to `path`: what `histo` prints for the file
+    written from them (count --histo, merge --histo)."""
+    base, bins, _ = counter.histo()
+    with open(path, "w") as fh:
+        fh.write(format_histo(base, 1, bins))
 
 
 def write_records(path, keys, counts, k, canonical, cmdline=None):

@@ -14,6 +14,8 @@
 //   jf_order_host.h  km_jf_*, km_counter_write_jf: files in Jellyfish's own record order (out through the same Staging)
 //   merge_host.h   km_jf_file_info, km_counter_add_records, km_counter_add_jf: records of existing tables, as pieces
 //                  on count_host.h's staging
+//   histo_host.h   km_histo_*, km_counter_histo, km_jf_histo: the count histogram and the four statistics of a counter
+//                  or a file in one streaming pass (its own two Staging buffers for a file)
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
 #include <hip/hip_runtime.h>
@@ -43,6 +45,8 @@
 #include "fastq_kernel.h"
 #include "fastx_strip.h"
 #include "graph_kernel.h"
+#include "histo_kernel.h"
+#include "histo_layout.h"
 #include "jf_order_kernel.h"
 #include "jf_reader.h"
 #include "kmin_kernel.h"
@@ -62,3 +66,4 @@ using namespace kmd;
 #include "count_host.h"
 #include "jf_order_host.h"
 #include "merge_host.h"
+#include "histo_host.h"

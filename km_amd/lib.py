@@ -41,6 +41,7 @@ SYMBOLS = [
     "km_jf_matrix", "km_jf_sort_records", "km_jf_sort_stats", "km_jf_sort_kernel_ms", "km_jf_header",
     "km_counter_write_jf",
     "km_jf_file_info", "km_counter_add_records", "km_counter_add_jf", "km_counter_merge_stats",
+    "km_histo_layout", "km_counter_histo", "km_jf_histo", "km_histo_kernel_ms", "km_histo_text", "km_histo_stats_text",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
 ]
 
@@ -74,6 +75,12 @@ class CounterStats(C.Structure):
     """km_counter_stats_t (include/kmgpu.h)."""
     _fields_ = [("bases", C.c_uint64), ("kmers", C.c_uint64), ("distinct", C.c_uint64), ("slots", C.c_uint64),
                 ("n_grow", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HistoStats(C.Structure):
+    """km_histo_stats_t (include/kmgpu.h)."""
+    _fields_ = [("unique", C.c_uint64), ("distinct", C.c_uint64), ("total", C.c_uint64), ("max_count", C.c_uint64),
+                ("reserved", C.c_uint64 * 2)]
 
 
 class TextState(C.Structure):
@@ -244,6 +251,13 @@ def load():
         "km_counter_add_records": [vp, vp, vp, u64, i32],
         "km_counter_add_jf": [vp, cp, i32, C.POINTER(u64)],
         "km_counter_merge_stats": [vp, C.POINTER(u64), C.POINTER(C.c_float)],
+        "km_histo_layout": [u64, u64, u64, C.POINTER(u64), C.POINTER(u64)],
+        "km_counter_histo": [vp, u64, u64, u64, u32, u32, vp, u64, C.POINTER(HistoStats)],
+        "km_jf_histo": [i32, cp, u64, u64, u64, u32, u32, vp, u64, C.POINTER(HistoStats), C.POINTER(C.c_int32),
+                        C.POINTER(u64), vp],
+        "km_histo_kernel_ms": [C.POINTER(C.c_float)],
+        "km_histo_text": [u64, u64, vp, u64, i32, vp, u64, C.POINTER(u64)],
+        "km_histo_stats_text": [C.POINTER(HistoStats), vp, u64, C.POINTER(u64)],
         "km_device_count": [C.POINTER(i32)],
         "km_device_sync": [i32],
         "km_device_copy_GBs": [i32, u64, i32, C.POINTER(dbl)],
@@ -585,6 +599,75 @@ class Counter:
         """km_counter_write_jf: the finished counter's records as a file in Jellyfish's own record order, sorted
         on the device and written natively (the records are not copied to the host as arrays)."""
         check(self._lib.km_counter_write_jf(self._c, os.fsencode(path), _cmdline_json(cmdline), int(seed)))
+
+
+    def histo(self, low=1, high=10000, increment=1, lower_count=1, upper_count=0xFFFFFFFF):
+        """km_counter_histo: the histogram of the counts and the four statistics, before finish() (everything added
+        so far; the counter is left as it was) or after it (the kept records) -> (base, bins uint64[n_bins], stats
+        dict).  A key takes part iff max(lower_count, 1) <= count <= upper_count; bin i is labelled
+        base + i * increment (include/kmgpu.h has the rule: this project's reading of `jellyfish histo`)."""
+        base, n_bins = histo_layout(low, high, increment)
+        bins = np.zeros(n_bins, np.uint64)
+        st = HistoStats()
+        check(self._lib.km_counter_histo(self._c, int(low), int(high), int(increment), int(lower_count),
+                                         int(upper_count), ptr(bins), bins.size, C.byref(st)))
+        return base, bins, _histo_stats_dict(st)
+
+
+def _histo_stats_dict(st):
+    return {"unique": int(st.unique), "distinct": int(st.distinct), "total": int(st.total),
+            "max_count": int(st.max_count)}
+
+
+def histo_layout(low=1, high=10000, increment=1):
+    """km_histo_layout -> (base, n_bins) of `histo -l low -h high -i increment` (host only)."""
+    base, n = C.c_uint64(), C.c_uint64()
+    check(load().km_histo_layout(int(low), int(high), int(increment), C.byref(base), C.byref(n)))
+    return int(base.value), int(n.value)
+
+
+def jf_histo(path, low=1, high=10000, increment=1, lower_count=1, upper_count=0xFFFFFFFF, device=0, stream=None):
+    """km_jf_histo: the same for the records of a `binary/sorted` file, streamed through the GPU piece by piece
+    -> (base, bins, stats dict with k and n_records of the header added)."""
+    base, n_bins = histo_layout(low, high, increment)
+    bins = np.zeros(n_bins, np.uint64)
+    st, k, n = HistoStats(), C.c_int32(), C.c_uint64()
+    check(load().km_jf_histo(int(device), os.fsencode(path), int(low), int(high), int(increment), int(lower_count),
+                             int(upper_count), ptr(bins), bins.size, C.byref(st), C.byref(k), C.byref(n),
+                             C.c_void_p(stream or 0)))
+    stats = _histo_stats_dict(st)
+    stats.update(k=int(k.value), n_records=int(n.value))
+    return base, bins, stats
+
+
+def histo_kernel_ms():
+    """km_histo_kernel_ms: the time of the histogram kernels of this thread's last Counter.histo / jf_histo."""
+    ms = C.c_float()
+    check(load().km_histo_kernel_ms(C.byref(ms)))
+    return float(ms.value)
+
+
+def histo_text(base, increment, bins, full=False):
+    """km_histo_text: "<label> <n>\\n" per bin with n > 0 (per bin with full), as str."""
+    lib = load()
+    bins = np.ascontiguousarray(bins, dtype=np.uint64)
+    ln = C.c_uint64()
+    args = (int(base), int(increment), ptr(bins) if bins.size else None, bins.size, int(bool(full)))
+    check(lib.km_histo_text(*args, None, 0, C.byref(ln)))
+    out = np.zeros(max(ln.value, 1), np.uint8)
+    check(lib.km_histo_text(*args, ptr(out), out.size, C.byref(ln)))
+    return out[:ln.value].tobytes().decode("ascii")
+
+
+def histo_stats_text(stats):
+    """km_histo_stats_text: the four lines of `jellyfish stats` for a stats dict of Counter.histo / jf_histo."""
+    lib = load()
+    st = HistoStats(int(stats["unique"]), int(stats["distinct"]), int(stats["total"]), int(stats["max_count"]))
+    ln = C.c_uint64()
+    check(lib.km_histo_stats_text(C.byref(st), None, 0, C.byref(ln)))
+    out = np.zeros(max(ln.value, 1), np.uint8)
+    check(lib.km_histo_stats_text(C.byref(st), ptr(out), out.size, C.byref(ln)))
+    return out[:ln.value].tobytes().decode("ascii")
 
 
 MERGE_MODES = {"sum": 0, "max": 1}         # KM_MERGE_SUM, KM_MERGE_MAX

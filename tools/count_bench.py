@@ -25,6 +25,14 @@ timed as wall time around calls that end in km_counter_stats (which waits for th
                input records/s, the time of the record kernel by HIP events (KM_COUNT_TIME_MERGE), best and all of
                --write-reps runs; and beside it the host path a user has today: Database.open(..).records() of both
                files combined with np.unique + np.add.at (host_merge_*)
+  histo      - the count histogram and the four statistics (Counter.histo, default layout): wall time and the time of
+               its kernel by HIP events (km_histo_kernel_ms), best and all of --write-reps runs, on the full counting
+               table before finish (table_*: a stream read of 16 * slots bytes, also given as GB/s and as a fraction
+               of the same run's km_device_copy_GBs) and on the kept counts after finish(2) (kept_*); histo_file of
+               the file write_jf wrote (file_*); the kernel time of each of the three also with 0..4 wave aggregation
+               rounds (*_kernel_ms_by_rounds, KM_HISTO_ROUNDS); and beside them the paths a user has today:
+               Counter.records() + np.bincount (host_records_*) and Database.open(path).records() + np.bincount
+               (host_open_*)
 and km_device_copy_GBs of the same run for scale.
 
 usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31] [--write-reps 3] [--text-reps 3]
@@ -135,8 +143,86 @@ def time_text_paths(k, device, text, reps):
     return out, stats["add_text"]
 
 
+def best_all(prefix, values):
+    return {prefix: min(values), prefix + "_all": values}
+
+
+def time_histo(call, reps):
+    """call() -> (base, bins, stats); wall seconds and kernel ms of every repeat, and the last result."""
+    wall, kernel, res = [], [], None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        res = call()
+        wall.append(time.perf_counter() - t0)
+        kernel.append(kmlib.histo_kernel_ms())
+    return wall, kernel, res
+
+
+def host_bincount(counts):
+    """What a user does today with the counts on the host: the default layout's bins and the four numbers."""
+    bins = np.bincount(np.minimum(counts, 10001).astype(np.int64), minlength=10002)[1:]
+    return bins, {"unique": int((counts == 1).sum()), "distinct": int(counts.size),
+                  "total": int(counts.sum(dtype=np.uint64)), "max_count": int(counts.max()) if counts.size else 0}
+
+
+def time_histo_table(counter, reps):
+    """Counter.histo() on the full counting table (before finish), and the same pass at 0..4 aggregation rounds."""
+    wall, kernel, res = time_histo(counter.histo, reps)
+    slots = counter.stats()["slots"]
+    sweep = {}
+    for rounds in range(5):
+        os.environ["KM_HISTO_ROUNDS"] = str(rounds)
+        sweep[str(rounds)] = time_histo(counter.histo, reps)[1]
+    os.environ.pop("KM_HISTO_ROUNDS", None)
+    return {**best_all("table_s", wall), **best_all("table_kernel_ms", kernel), "table_slots": slots,
+            "table_bytes": 16 * slots, "table_GBs": 16 * slots / (min(kernel) * 1e-3) / 1e9,
+            "table_kernel_ms_by_rounds": sweep, "table_stats": res[2]}
+
+
+def time_histo_kept(counter, reps):
+    """Counter.histo() after finish, against Counter.records() + np.bincount."""
+    wall, kernel, res = time_histo(counter.histo, reps)
+    sweep = {}
+    for rounds in range(5):
+        os.environ["KM_HISTO_ROUNDS"] = str(rounds)
+        sweep[str(rounds)] = time_histo(counter.histo, reps)[1]
+    os.environ.pop("KM_HISTO_ROUNDS", None)
+    host = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        _, counts = counter.records()
+        bins, stats = host_bincount(counts)
+        host.append(time.perf_counter() - t0)
+    assert np.array_equal(bins, res[1].astype(bins.dtype)) and stats == res[2]
+    return {**best_all("kept_s", wall), **best_all("kept_kernel_ms", kernel), "kept_stats": res[2],
+            "kept_kernel_ms_by_rounds": sweep,
+            **best_all("host_records_s", host)}
+
+
+def time_histo_file(path, device, reps):
+    """histo_file of a written file, against Database.open(path).records() + np.bincount."""
+    wall, kernel, res = time_histo(lambda: kc.histo_file(path, device=device), reps)
+    sweep = {}
+    for rounds in range(5):
+        os.environ["KM_HISTO_ROUNDS"] = str(rounds)
+        sweep[str(rounds)] = time_histo(lambda: kc.histo_file(path, device=device), reps)[1]
+    os.environ.pop("KM_HISTO_ROUNDS", None)
+    host = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        db = kmlib.Database.open(path)
+        _, counts = db.records()
+        bins, stats = host_bincount(counts)
+        db.close()
+        host.append(time.perf_counter() - t0)
+    assert np.array_equal(bins, res[1].astype(bins.dtype)) and all(stats[key] == res[2][key] for key in stats)
+    return {**best_all("file_s", wall), **best_all("file_kernel_ms", kernel), "file_bytes": os.path.getsize(path),
+            "file_kernel_ms_by_rounds": sweep,
+            **best_all("host_open_s", host)}
+
+
 def time_writers(counter, k, reps):
-    """The field group of the two file writers on a finished counter."""
+    """The field group of the two file writers on a finished counter (and, on the file they leave, histo_file)."""
     tmp = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else tempfile.gettempdir()
     path = os.path.join(tmp, "count_bench_%d.jf" % os.getpid())
     native, kernels, host, parts = [], [], [], None
@@ -157,6 +243,7 @@ def time_writers(counter, k, reps):
             host.append(t2 - t0)
             if parts is None or host[-1] <= min(host):
                 parts = {"records_s": t1 - t0, "write_records_s": t2 - t1}
+        histo_file = time_histo_file(path, counter.device, reps)
     finally:
         if os.path.exists(path):
             os.unlink(path)
@@ -167,7 +254,7 @@ def time_writers(counter, k, reps):
         "write_jf_buckets": stats["buckets"], "write_jf_largest_bucket": stats["largest"],
         "write_jf_oversized_buckets": stats["oversized"],
         "host_sorted_s": min(host), "host_sorted_s_all": host, "host_sorted_parts": parts,
-    }
+    }, histo_file
 
 
 def time_merge(stream, k, device, reps):
@@ -241,12 +328,15 @@ def run_size(name, k, device, rng, write_reps=3, text_reps=3):
     sized.add_bases(stream)
     st = sized.stats()
     t_bases = time.perf_counter() - t0
+    histo = time_histo_table(sized, write_reps)
     t0 = time.perf_counter()
     db = sized.finish(2)
     t_finish = time.perf_counter() - t0
     n_kept = int(db.info.n_records)
     db.close()
-    writers = time_writers(sized, k, write_reps)
+    histo.update(time_histo_kept(sized, write_reps))
+    writers, histo_file = time_writers(sized, k, write_reps)
+    histo.update(histo_file)
     sized.close()
 
     merged = time_merge(stream, k, device, write_reps)
@@ -263,6 +353,7 @@ def run_size(name, k, device, rng, write_reps=3, text_reps=3):
         "finish_s": t_finish,
         **writers,
         **merged,
+        "histo": histo,
     }
 
 
@@ -280,6 +371,8 @@ def main():
     for name in args.sizes.split(","):
         out["sizes"][name] = run_size(name, args.k, args.device, rng, args.write_reps, args.text_reps)
     out["km_device_copy_GBs"] = kmlib.device_copy_GBs(args.device, 1 << 30, 10)
+    for size in out["sizes"].values():
+        size["histo"]["table_fraction_of_copy"] = size["histo"]["table_GBs"] / out["km_device_copy_GBs"]
     print(json.dumps(out))
 
 

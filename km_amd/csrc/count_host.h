@@ -8,10 +8,10 @@
 // piece i covers [i (S - k + 1), i (S - k + 1) + S), so a window of k bytes lies wholly inside exactly one piece.
 // km_counter_add_fastq stages raw FASTQ text instead, in pieces of whole records that overlap by nothing, and the
 // device turns each piece into such a byte stream of its own (fastq_kernel.h) in front of the same insert kernel.
-// Whatever is staged, text, FASTQ or the records of merge_host.h, takes one way to the device: Staging::claim, fill
-// Staging::mine, counter_ship, then the producer's own kernels.
+// Whatever is staged, text, FASTQ or the records of merge_host.h, takes one way to the device, that of Staging
+// (host_common.h, with the rule that holds the buffers together): claim, fill `mine`, counter_reserve, ship to d_text
+// on the counter's stream, then the producer's own kernels.
 namespace {
-constexpr uint64_t COUNT_STAGE_BYTES = 16ull << 20;     // per pinned buffer (KM_COUNT_STAGE_BYTES: tests)
 constexpr uint64_t COUNT_DEFAULT_SLOTS = 1ull << 16;
 uint64_t key_space(int k) { return k >= 32 ? ~0ull : (1ull << (2 * k)); }
 
@@ -20,24 +20,6 @@ struct FastqDev {
   DevBuf<uint8_t> masked;                 // the piece as k_count_insert reads it (k_fq_mask's output)
   DevBuf<uint32_t> tiles, sums;           // newlines per tile, scanned in place (k_scan_*), and the chunk sums
   DevBuf<uint32_t> line_start;
-};
-
-// The two pinned buffers through which everything reaches the device, taking turns.  One rule holds them together:
-// the host writes a buffer only once the copy out of it is done.  Producers write through `mine` alone: claim() sets
-// it once the buffer whose turn it is has been waited for, counter_ship takes it away again, and it is null in
-// between, so no producer can write under a copy.  (km_counter_write_jf runs the same buffers and events the other
-// way, device to host, once the counter has finished.)
-struct Staging {
-  Pinned pin[2];
-  Event copied[2];                        // the copy out of pin[i] is done
-  uint64_t bytes = COUNT_STAGE_BYTES;     // per buffer
-  int cur = 0;                            // whose turn it is
-  unsigned char* mine = nullptr;          // pin[cur] while it is the host's to write
-  int claim() {
-    HIPCHK(hipEventSynchronize(copied[cur]));
-    mine = pin[cur];
-    return KM_OK;
-  }
 };
 
 const char* fastq_error_text(unsigned kind) {
@@ -144,18 +126,6 @@ static int counter_reserve(km_counter* c, uint64_t windows) {
   return KM_OK;
 }
 
-// The n bytes the host wrote to the claimed buffer go to d_text, and the turn passes to the other buffer.
-// new_keys: the most keys the piece can add (counter_reserve, which may wait for the stream and rehash first).
-static int counter_ship(km_counter* c, uint64_t n, uint64_t new_keys) {
-  Staging& s = c->stg;
-  KMCHK(counter_reserve(c, new_keys));
-  HIPCHK(hipMemcpyAsync(c->d_text, s.mine, n, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipEventRecord(s.copied[s.cur], c->st));
-  s.mine = nullptr;
-  s.cur ^= 1;
-  return KM_OK;
-}
-
 // text[0 .. n) on the device into the table; the windows that start before own_from belong to the piece before.
 static int launch_insert(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from) {
   const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
@@ -171,7 +141,8 @@ static int counter_flush(km_counter* c) {
   if (c->fill <= c->own_from) return KM_OK;
   const uint64_t n = c->fill;
   const unsigned char* sent = c->stg.mine;            // (a buffer whose copy is in flight may still be read)
-  KMCHK(counter_ship(c, n, n >= (uint64_t)c->k ? n - c->k + 1 : 0));
+  KMCHK(counter_reserve(c, n >= (uint64_t)c->k ? n - c->k + 1 : 0));
+  KMCHK(c->stg.ship(c->d_text, n, c->st));
   KMCHK(launch_insert(c, c->d_text, n, c->own_from));
   KMCHK(c->stg.claim());
   const uint64_t keep = std::min<uint64_t>((uint64_t)c->k - 1, n);
@@ -217,8 +188,6 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
   c->device = device;
   c->k = k;
   c->canonical = canonical ? 1 : 0;
-  Staging& s = c->stg;
-  if (const char* e = getenv("KM_COUNT_STAGE_BYTES")) s.bytes = std::max<uint64_t>(256, strtoull(e, nullptr, 10));
   if (const char* e = getenv("KM_COUNT_TIME_MERGE")) c->merge_spans.timed = atoi(e) != 0;
   c->slots = COUNT_DEFAULT_SLOTS;
   if (expected_distinct) {
@@ -228,13 +197,9 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
   HIPCHK(hipStreamCreateWithFlags(&c->st.h, hipStreamNonBlocking));
   int rc = c->table.alloc(c->slots);
   if (rc == KM_OK) rc = c->meta.alloc(CM_WORDS);
-  if (rc == KM_OK) rc = c->d_text.alloc(s.bytes + COUNT_PAD);
+  if (rc == KM_OK) rc = c->d_text.alloc(c->stg.bytes + COUNT_PAD);
+  if (rc == KM_OK) rc = c->stg.alloc(COUNT_PAD);
   if (rc != KM_OK) return rc;
-  for (int i = 0; i < 2; ++i) {
-    hipError_t e = hipHostMalloc((void**)&s.pin[i].h, s.bytes + COUNT_PAD, hipHostMallocDefault);
-    if (e != hipSuccess) { s.pin[i].h = nullptr; return fail(KM_E_NOMEM, "pinned staging buffer: %s", hipGetErrorString(e)); }
-    HIPCHK(hipEventCreateWithFlags(&s.copied[i].h, hipEventDisableTiming));
-  }
   HIPCHK(hipMemsetAsync(c->meta, 0, CM_WORDS * 8, c->st));
   HIPCHK(hipMemsetAsync(c->meta.p + CM_FORMAT, 0xFF, 8, c->st));        // FQ_NO_ERROR
   hipLaunchKernelGGL(k_count_init, dim3(grid_for(c->slots, 256)), dim3(256), 0, c->st, c->table.p, c->slots);
@@ -313,7 +278,8 @@ static int fastq_enqueue(km_counter* c, const char* text, uint64_t n, uint64_t b
   FastqDev& f = *c->fq;
   KMCHK(c->stg.claim());
   memcpy(c->stg.mine, text, n);
-  KMCHK(counter_ship(c, n, n));                         // every byte taken as a window: a bound, and a loose one
+  KMCHK(counter_reserve(c, n));                         // every byte taken as a window: a bound, and a loose one
+  KMCHK(c->stg.ship(c->d_text, n, c->st));
   const uint32_t n_tiles = (uint32_t)((n + FQ_TILE - 1) / FQ_TILE);
   const uint32_t n_chunks = (uint32_t)(((uint64_t)n_tiles + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK);
   KMCHK(c->fq_spans.open(c->st));

@@ -1,5 +1,5 @@
-// db_host.h — the database: kmjf_* open / upload / broadcast / load and the lookups (host part of kmgpu.hip;
-// device side: table_kernels.h)
+// db_host.h — the database: kmjf_* open / upload / broadcast / load and the lookups; RecordFile, the one reader of a
+// file's record area (host part of kmgpu.hip; device side: table_kernels.h)
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
@@ -81,14 +81,26 @@ static int reader_result(int rc, const std::string& err, int k) {
   return KM_OK;
 }
 
-// The header of `path` as kmjf_open judges it; *f is left open, positioned anywhere.
-static int open_layout(const char* path, jfio::Layout* lay, File* f) {
-  std::string err;
-  void* file = nullptr;
-  const int rc = jfio::read_layout(path, lay, &file, &err);
-  f->h = static_cast<FILE*>(file);
-  return reader_result(rc, err, lay->k);
-}
+// The record area of a file, for the calls that take it in as it is stored, whole or piece by piece.
+struct RecordFile {
+  jfio::Layout lay;
+  File f;                                 // left open by open(), positioned anywhere
+  const char* path = nullptr;             // (the caller's, for the messages)
+  uint64_t rec = 0;                       // bytes per record
+  int open(const char* p) {               // the header of `p` as kmjf_open judges it
+    std::string err;
+    void* file = nullptr;
+    const int rc = jfio::read_layout(path = p, &lay, &file, &err);
+    f.h = static_cast<FILE*>(file);
+    rec = (uint64_t)lay.key_bytes + lay.counter_bytes;
+    return reader_result(rc, err, lay.k);
+  }
+  int read(const kmpiece::Piece& p, unsigned char* dst) const {   // the records of piece p into dst[p.bytes]
+    const int e = kmpiece::read_exact(fileno(f), dst, p.bytes, lay.body_offset + p.first * rec);
+    if (e == 0) return KM_OK;
+    return fail(KM_E_IO, "reading the records of %s failed: %s", path, e < 0 ? "the file ends early" : strerror(e));
+  }
+};
 
 extern "C" int kmjf_open(const char* path, kmjf_t** out) {
   if (!path || !out) return fail(KM_E_ARG, "null argument");
@@ -492,23 +504,23 @@ extern "C" int kmjf_broadcast(kmjf_t* h, const int* devices, int n, kmjf_t** rep
 // reports none).  Measured (bench.py `jf_ingestion`) against the host reader + upload.
 extern "C" int kmjf_load(const char* path, int device, kmjf_t** out) {
   if (!path || !out) return fail(KM_E_ARG, "null argument");
-  jfio::Layout lay;
-  File f;
-  int rc = open_layout(path, &lay, &f);
+  RecordFile file;
+  int rc = file.open(path);
   if (rc != KM_OK) return rc;
+  const jfio::Layout& lay = file.lay;
   const uint64_t n = lay.n_records;
-  const uint64_t rec = (uint64_t)lay.key_bytes + lay.counter_bytes;
+  const uint64_t rec = file.rec;
   const uint64_t body = n * rec;
   // map the whole file (the record area does not start on a page boundary)
   const uint64_t map_len = lay.body_offset + body;
   Mapping map(nullptr, Unmap{map_len});
   if (body) {
-    void* m = mmap(nullptr, map_len, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fileno(f), 0);   // populate: no per-page faults during the copy
+    void* m = mmap(nullptr, map_len, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fileno(file.f), 0);   // populate: no per-page faults during the copy
     if (m == MAP_FAILED) return fail(KM_E_IO, "cannot map %s", path);
     map.reset(m);
     (void)madvise(m, map_len, MADV_SEQUENTIAL);
   }
-  f.reset();                                   // the mapping stays valid
+  file.f.reset();                              // the mapping stays valid
 
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail_hip(KM_E_HIP, "device setup failed", e);

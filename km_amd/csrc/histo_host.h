@@ -2,8 +2,9 @@
 // of kmgpu.hip; device side: histo_kernel.h; the bin rule, its checks and the text: histo_layout.h)
 // ------------------------------------------------------------------ histogram of counts and table statistics
 // One streaming pass over counts that already sit in HBM — the counting table of a live counter, the kept counts of a
-// finished one — or over the record area of a file as it comes through two pinned buffers.  Nothing is changed: a
-// live counter takes further add_* and finish afterwards.
+// finished one — or over the record area of a file as it comes, piece by piece (merge_pieces.h), out of a RecordFile
+// (db_host.h) through a Staging of the call's own (host_common.h) on a CallStream.  Nothing is changed: a live counter
+// takes further add_* and finish afterwards.
 namespace {
 thread_local float g_histo_kernel_ms = 0.f;
 
@@ -189,63 +190,38 @@ extern "C" int km_jf_histo(int device, const char* path, uint64_t low, uint64_t 
   kmhisto::Layout lay;
   HistoRule r;
   KMCHK(histo_rule(low, high, increment, lower_count, upper_count, &lay, &r));
-  jfio::Layout file;
-  File f;
-  KMCHK(open_layout(path, &file, &f));
+  RecordFile file;
+  KMCHK(file.open(path));
   KMCHK(histo_capacity(lay, bins, cap));
-  if (k) *k = file.k;
-  if (n_records) *n_records = file.n_records;
+  const uint64_t n = file.lay.n_records, rec = file.rec;
+  if (k) *k = file.lay.k;
+  if (n_records) *n_records = n;
   r.rounds = histo_rounds();
   g_histo_kernel_ms = 0.f;
-  if (file.n_records == 0) { histo_zeros(lay, bins, stats); return KM_OK; }
-  const uint32_t kb = file.key_bytes, cb = file.counter_bytes;
-  const uint64_t rec = (uint64_t)kb + cb;
+  if (n == 0) { histo_zeros(lay, bins, stats); return KM_OK; }
+  const uint32_t kb = file.lay.key_bytes, cb = file.lay.counter_bytes;
   Staging s;
-  if (const char* e = getenv("KM_COUNT_STAGE_BYTES")) s.bytes = std::max<uint64_t>(256, strtoull(e, nullptr, 10));
   // (a piece is ONE launch: at most HISTO_CHUNK records, the bound of histo_kernel.h on the items of a launch)
   const uint64_t per = std::min(kmpiece::per_piece(s.bytes, rec), HISTO_CHUNK);
   if (per == 0) return fail(KM_E_ARG, "records of %llu bytes do not fit a staging buffer", (unsigned long long)rec);
-  HIPCHK(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  bool own_stream = false;
-  if (!st) {
-    KMCHK(pool_get(device, &st));
-    own_stream = true;
-  }
-  struct GiveBack {                                     // (declared before what runs on the stream: released after it)
-    hipStream_t st; bool own;
-    ~GiveBack() { if (own && !pool_give_back(st)) (void)hipStreamDestroy(st); }
-  } give_back{st, own_stream};
+  CallStream st;                                        // (declared before what runs on the stream: released after it)
+  KMCHK(st.get(device, stream));
   struct Drain {                                        // no early return leaves a copy out of a freed buffer in flight
     hipStream_t st;
     ~Drain() { (void)hipStreamSynchronize(st); }
   };
   DevBuf<uint8_t> d_raw;
   HistoRun run;
-  for (int i = 0; i < 2; ++i) {
-    hipError_t e = hipHostMalloc((void**)&s.pin[i].h, s.bytes, hipHostMallocDefault);
-    if (e != hipSuccess) { s.pin[i].h = nullptr; return fail(KM_E_NOMEM, "pinned staging buffer: %s", hipGetErrorString(e)); }
-    HIPCHK(hipEventCreateWithFlags(&s.copied[i].h, hipEventDisableTiming));
-  }
+  KMCHK(s.alloc(0));
   KMCHK(d_raw.alloc(s.bytes));
   Drain drain{st};
   KMCHK(run.begin(r.n_bins, st));
-  const int fd = fileno(f);
-  const uint64_t pieces = kmpiece::n_pieces(file.n_records, per);
+  const uint64_t pieces = kmpiece::n_pieces(n, per);
   for (uint64_t i = 0; i < pieces; ++i) {
-    const kmpiece::Piece p = kmpiece::piece(file.n_records, per, rec, i);
+    const kmpiece::Piece p = kmpiece::piece(n, per, rec, i);
     KMCHK(s.claim());                                   // the copy out of this buffer, two pieces ago, is done
-    for (uint64_t got = 0; got < p.bytes;) {
-      const ssize_t n = pread(fd, s.mine + got, p.bytes - got, (off_t)(file.body_offset + p.first * rec + got));
-      if (n < 0 && errno == EINTR) continue;
-      if (n <= 0) return fail(KM_E_IO, "reading the records of %s failed: %s", path,
-                              n < 0 ? strerror(errno) : "the file ends early");
-      got += (uint64_t)n;
-    }
-    HIPCHK(hipMemcpyAsync(d_raw, s.mine, p.bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(s.copied[s.cur], st));
-    s.mine = nullptr;
-    s.cur ^= 1;
+    KMCHK(file.read(p, s.mine));
+    KMCHK(s.ship(d_raw, p.bytes, st));
     const uint64_t items = (kb == 8 && cb == 4) ? std::max<uint64_t>(p.records / 4, 1) : p.records;
     KMCHK(run.spans.open(st));
     hipLaunchKernelGGL(k_histo_records, dim3(histo_grid(items)), dim3(HISTO_THREADS), 0, st, d_raw.p, p.records, kb, cb, r,

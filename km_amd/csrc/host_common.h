@@ -1,4 +1,4 @@
-// host_common.h — what every host part of kmgpu.hip shares: error plumbing, owned resources, the stream pool
+// host_common.h — what every host part of kmgpu.hip shares: error plumbing, owned resources, Staging, the stream pool
 // ------------------------------------------------------------------ error plumbing
 static thread_local std::string g_last_error;
 
@@ -143,6 +143,50 @@ struct KernelSpans {
     return KM_OK;
   }
 };
+
+// Two pinned buffers that take turns between the host and a stream, and an event per buffer: the copy that last
+// used it is done.  One rule holds them together, in either direction: the host touches a buffer only once that
+// copy is done.  It therefore gets a buffer's address from claim() or wait() alone, which wait for the event first.
+// Host to device (a counter's text, FASTQ and record pieces; km_jf_histo): producers write through `mine`, which
+// claim() sets to the buffer whose turn it is and ship() takes away again, so it is null in between and no producer
+// can write under a copy.  Device to host (km_counter_write_jf, once the counter has finished): fetch(buf) enqueues
+// the copy into a buffer and wait(buf) hands it out to be read.
+constexpr uint64_t COUNT_STAGE_BYTES = 16ull << 20;     // per pinned buffer
+struct Staging {
+  Pinned pin[2];
+  Event copied[2];                        // the copy out of, or into, pin[i] is done
+  uint64_t bytes = COUNT_STAGE_BYTES;     // per buffer (KM_COUNT_STAGE_BYTES: tests reach many pieces with small inputs)
+  int cur = 0;                            // whose turn it is
+  unsigned char* mine = nullptr;          // pin[cur] while it is the host's to write
+  Staging() { if (const char* e = getenv("KM_COUNT_STAGE_BYTES")) bytes = std::max<uint64_t>(256, strtoull(e, nullptr, 10)); }
+  int alloc(uint64_t pad) {               // the buffers, of bytes + pad each, and their events
+    for (int i = 0; i < 2; ++i) {
+      hipError_t e = hipHostMalloc((void**)&pin[i].h, bytes + pad, hipHostMallocDefault);
+      if (e != hipSuccess) { pin[i].h = nullptr; return fail(KM_E_NOMEM, "pinned staging buffer: %s", hipGetErrorString(e)); }
+      HIPCHK(hipEventCreateWithFlags(&copied[i].h, hipEventDisableTiming));
+    }
+    return KM_OK;
+  }
+  int claim() { return wait(cur, &mine); }
+  // The n bytes the host wrote to the claimed buffer go to d_dst on st, and the turn passes to the other buffer.
+  int ship(void* d_dst, uint64_t n, hipStream_t st) {
+    HIPCHK(hipMemcpyAsync(d_dst, mine, n, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(copied[cur], st));
+    mine = nullptr;
+    cur ^= 1;
+    return KM_OK;
+  }
+  int fetch(int buf, const void* d_src, uint64_t n, hipStream_t st) {
+    HIPCHK(hipMemcpyAsync(pin[buf], d_src, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(copied[buf], st));
+    return KM_OK;
+  }
+  int wait(int buf, unsigned char** ready) {
+    HIPCHK(hipEventSynchronize(copied[buf]));
+    *ready = pin[buf];
+    return KM_OK;
+  }
+};
 }  // namespace
 
 // ---- streams.  A pipelined consumer runs a few batches at a time, each on its own launch stream.  How
@@ -193,6 +237,21 @@ bool pool_give_back(hipStream_t st) {
       if (kv.second.launch[i] == st) { kv.second.in_use[i] = 0; return true; }
   return false;
 }
+
+// The stream of one call, read as the handle like the owners above: the caller's, or one of the pool's for as long as
+// the call lasts.  Declared before whatever runs on the stream, so that it is released after it.
+struct CallStream {
+  hipStream_t st = nullptr;
+  bool own = false;
+  ~CallStream() { if (own && !pool_give_back(st)) (void)hipStreamDestroy(st); }
+  operator hipStream_t() const { return st; }
+  int get(int device, void* stream) {      // makes `device` current
+    HIPCHK(hipSetDevice(device));
+    st = (hipStream_t)stream;
+    if (!st) { KMCHK(pool_get(device, &st)); own = true; }
+    return KM_OK;
+  }
+};
 }  // namespace
 
 extern "C" int km_stream_create(int device, void** stream) {

@@ -180,17 +180,8 @@ extern "C" int km_jf_sort_records(int device, const uint64_t* columns, int k, in
   memset(g_jf_stats, 0, sizeof g_jf_stats);
   g_jf_kernel_ms = 0.f;
   if (n == 0) return KM_OK;
-  HIPCHK(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  bool own_stream = false;
-  if (!st) {
-    KMCHK(pool_get(device, &st));
-    own_stream = true;
-  }
-  struct GiveBack {
-    hipStream_t st; bool own;
-    ~GiveBack() { if (own && !pool_give_back(st)) (void)hipStreamDestroy(st); }
-  } give_back{st, own_stream};
+  CallStream st;
+  KMCHK(st.get(device, stream));
   const uint64_t rec = (uint64_t)(2 * k + 7) / 8 + 4;
   DevBuf<uint64_t> d_keys, d_pos;
   DevBuf<uint32_t> d_counts;
@@ -208,8 +199,8 @@ extern "C" int km_jf_sort_records(int device, const uint64_t* columns, int k, in
   return KM_OK;
 }
 
-// The sorted records leave the device through the counter's two pinned staging buffers, which are idle once the
-// counter has finished: the copy of one piece runs while the piece before it is written to the file.
+// The sorted records leave the device through the counter's Staging (fetch and wait: host_common.h), which is idle
+// once the counter has finished: the copy of one piece runs while the piece before it is written to the file.
 extern "C" int km_counter_write_jf(km_counter_t* c, const char* path, const char* cmdline_json, uint64_t seed) {
   if (!c || !path) return fail(KM_E_ARG, "null argument");
   if (!c->finished) return fail(KM_E_STATE, "km_counter_finish comes first");
@@ -243,17 +234,14 @@ extern "C" int km_counter_write_jf(km_counter_t* c, const char* path, const char
   bool ok = put(header.data(), header.size());
   Staging& s = c->stg;
   const uint64_t piece = s.bytes;
-  auto enqueue = [&](uint64_t at, int buf) -> hipError_t {
-    hipError_t e = hipMemcpyAsync(s.pin[buf], d_records.p + at, std::min(piece, total - at), hipMemcpyDeviceToHost, c->st);
-    return e != hipSuccess ? e : hipEventRecord(s.copied[buf], c->st);
-  };
+  auto fetch = [&](uint64_t at, int buf) { return s.fetch(buf, d_records.p + at, std::min(piece, total - at), c->st); };
   int cur = 0;
-  if (total) HIPCHK(enqueue(0, 0));
+  if (total) KMCHK(fetch(0, 0));
   for (uint64_t at = 0; at < total && ok; at += piece, cur ^= 1) {
-    if (at + piece < total) HIPCHK(enqueue(at + piece, cur ^ 1));
-    HIPCHK(hipEventSynchronize(s.copied[cur]));
-    const uint64_t len = std::min(piece, total - at);
-    ok = put(s.pin[cur], len);
+    if (at + piece < total) KMCHK(fetch(at + piece, cur ^ 1));
+    unsigned char* got = nullptr;
+    KMCHK(s.wait(cur, &got));
+    ok = put(got, std::min(piece, total - at));
   }
   if (total) HIPCHK(hipStreamSynchronize(c->st));
   if (fclose(f.take()) != 0 && ok) {

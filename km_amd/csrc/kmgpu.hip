@@ -2,20 +2,21 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -fPIC -shared (see __graft_entry__.build()).
 // One translation unit; the host code is in the parts included at the bottom, one per subsystem:
 //   host_common.h  error plumbing, owners of device memory / events / streams, KernelSpans (timing by event pairs),
-//                  the stream pool, km_stream_*
+//                  Staging (two pinned buffers taking turns, either direction, and the one rule that governs them),
+//                  the stream pool, CallStream (the caller's stream or one of the pool's), km_stream_*
 //   db_host.h      the database: kmjf_* open / upload / broadcast / load, the lookups; what the file readers return
-//                  as the library's codes (reader_result, open_layout)
+//                  as the library's codes (reader_result); RecordFile, the one reader of a file's record area
 //   tier_geometry.h  what the LDS tier can hold (constants, fast_tier_fits)
 //   batch_host.h   knobs, km_batch (what a batch owns), set_targets, one step: km_batch_run, km_batch_sync
 //   result_host.h  reading a delivered step: km_batch_result / _pump / _fetch, diagnostics and measurement exports
 //   kmin_host.h    km_linear_kmin
-//   count_host.h   km_counter_*, km_text_strip, km_fastq_cut; Staging, the one way of text, FASTQ and record pieces
-//                  through the counter's two pinned buffers (claim, counter_ship, counter_begin_pieces)
+//   count_host.h   km_counter_*, km_text_strip, km_fastq_cut; the one way of text, FASTQ and record pieces through the
+//                  counter's Staging (claim, counter_reserve, ship; counter_begin_pieces)
 //   jf_order_host.h  km_jf_*, km_counter_write_jf: files in Jellyfish's own record order (out through the same Staging)
 //   merge_host.h   km_jf_file_info, km_counter_add_records, km_counter_add_jf: records of existing tables, as pieces
-//                  on count_host.h's staging
+//                  on the counter's staging
 //   histo_host.h   km_histo_*, km_counter_histo, km_jf_histo: the count histogram and the four statistics of a counter
-//                  or a file in one streaming pass (its own two Staging buffers for a file)
+//                  or a file in one streaming pass (a file: RecordFile, a Staging of the call's own, CallStream)
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
 #include <hip/hip_runtime.h>

@@ -46,17 +46,8 @@ extern "C" int km_linear_kmin(int device, const uint8_t* bases, const uint64_t* 
   max_targets = std::max(max_targets, n_targets - chunk_first.back());
   chunk_first.push_back(n_targets);
 
-  HIPCHK(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  bool own_stream = false;
-  if (!st) {
-    KMCHK(pool_get(device, &st));
-    own_stream = true;
-  }
-  struct GiveBack {
-    hipStream_t st; bool own;
-    ~GiveBack() { if (own && !pool_give_back(st)) (void)hipStreamDestroy(st); }
-  } give_back{st, own_stream};
+  CallStream st;
+  KMCHK(st.get(device, stream));
 
   struct {
     DevBuf<uint8_t> text;

@@ -1,7 +1,7 @@
 // merge_host.h — km_jf_file_info, km_counter_add_records, km_counter_add_jf, km_counter_merge_stats (host part of
-// kmgpu.hip; device side: merge_kernel.h; the piece arithmetic: merge_pieces.h)
+// kmgpu.hip; device side: merge_kernel.h; the piece arithmetic: merge_pieces.h; a file's records: db_host.h)
 // ------------------------------------------------------------------ records of existing tables into a counter
-// A record area, of a file or packed from host arrays, goes through the counter's staging (count_host.h) into d_text
+// A record area, of a file or packed from host arrays, goes through the counter's Staging (host_common.h) into d_text
 // in pieces of whole records (the staging size rounded down to a multiple of the record size), each followed by
 // k_count_add_records on the counter's stream: copy, event, kernel.  The host fills the next piece while the last
 // one runs; nothing waits except counter_reserve when it has to read the occupancy.
@@ -23,7 +23,8 @@ int merge_enqueue(km_counter* c, uint64_t n, uint32_t kb, uint32_t cb, int mode,
     const kmpiece::Piece p = kmpiece::piece(n, per, rec, i);
     KMCHK(c->stg.claim());
     KMCHK(fill(c->stg.mine, p));
-    KMCHK(counter_ship(c, p.bytes, p.records));         // every record a new key: the insert never meets a full table
+    KMCHK(counter_reserve(c, p.records));               // every record a new key: the insert never meets a full table
+    KMCHK(c->stg.ship(c->d_text, p.bytes, c->st));
     KMCHK(c->merge_spans.open(c->st));
     hipLaunchKernelGGL(k_count_add_records, dim3(grid_for(p.records, 256)), dim3(256), 0, c->st, c->d_text.p, p.records,
                        kb, cb, mode, c->table.p, c->slots - 1, c->meta.p);
@@ -37,9 +38,9 @@ int merge_enqueue(km_counter* c, uint64_t n, uint32_t kb, uint32_t cb, int mode,
 extern "C" int km_jf_file_info(const char* path, int32_t* k, int32_t* canonical, uint64_t* n_records, int32_t* key_bytes,
                                int32_t* counter_len) {
   if (!path) return fail(KM_E_ARG, "null argument");
-  jfio::Layout lay;
-  File f;
-  KMCHK(open_layout(path, &lay, &f));
+  RecordFile file;
+  KMCHK(file.open(path));
+  const jfio::Layout& lay = file.lay;
   if (k) *k = lay.k;
   if (canonical) *canonical = lay.canonical;
   if (n_records) *n_records = lay.n_records;
@@ -62,27 +63,16 @@ extern "C" int km_counter_add_records(km_counter_t* c, const uint64_t* keys, con
 extern "C" int km_counter_add_jf(km_counter_t* c, const char* path, int mode, uint64_t* n_records) {
   if (!c || !path) return fail(KM_E_ARG, "null argument");
   KMCHK(merge_check(c, mode));
-  jfio::Layout lay;
-  File f;
-  KMCHK(open_layout(path, &lay, &f));
+  RecordFile file;
+  KMCHK(file.open(path));
+  const jfio::Layout& lay = file.lay;
   if (lay.k != c->k || lay.canonical != c->canonical)
     return fail(KM_E_ARG, "%s holds k=%d canonical=%d, the counter k=%d canonical=%d", path, lay.k, lay.canonical, c->k,
                 c->canonical);
   if (n_records) *n_records = lay.n_records;
   if (lay.n_records == 0) return KM_OK;
-  const int fd = fileno(f);
-  const uint64_t rec = (uint64_t)lay.key_bytes + lay.counter_bytes;
   return merge_enqueue(c, lay.n_records, lay.key_bytes, lay.counter_bytes, mode,
-                       [&](unsigned char* dst, const kmpiece::Piece& p) {
-                         for (uint64_t got = 0; got < p.bytes;) {
-                           const ssize_t r = pread(fd, dst + got, p.bytes - got, (off_t)(lay.body_offset + p.first * rec + got));
-                           if (r < 0 && errno == EINTR) continue;
-                           if (r <= 0) return fail(KM_E_IO, "reading the records of %s failed: %s", path,
-                                                   r < 0 ? strerror(errno) : "the file ends early");
-                           got += (uint64_t)r;
-                         }
-                         return KM_OK;
-                       });
+                       [&](unsigned char* dst, const kmpiece::Piece& p) { return file.read(p, dst); });
 }
 
 extern "C" int km_counter_merge_stats(km_counter_t* c, uint64_t* records_in, float* kernel_ms) {

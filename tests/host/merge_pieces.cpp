@@ -6,7 +6,10 @@
 // merge_enqueue does — each piece copied into a heap buffer of EXACTLY the staging size, so a piece that is a byte
 // too long is a heap overflow the sanitizer reports — and checks that the pieces are whole records, in order,
 // without gap or overlap, that only the last one is short, and that what arrives is what was sent.  Then the same
-// for host arrays packed into 12-byte records.  Prints "PIECES OK".
+// for host arrays packed into 12-byte records, and read_exact (the one loop over pread, under RecordFile::read) over
+// a temporary file, into heap buffers of exactly the length asked for.  Prints "PIECES OK".
+#include <fcntl.h>
+
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -82,7 +85,51 @@ static int walk_arrays(uint64_t stage) {
   return 0;
 }
 
+// read_exact over a file of a 9 + 5 byte header and 96 bytes of records (12 records of 8 bytes)
+static int read_area() {
+  char path[] = "/tmp/merge_pieces_XXXXXX";
+  const int fd = mkstemp(path);
+  REQUIRE(fd >= 0);
+  const uint64_t header = 9 + 5, body = 96;
+  std::vector<unsigned char> file(header + body);
+  for (uint64_t i = 0; i < file.size(); ++i) file[i] = (unsigned char)mix(i);
+  const bool written = write(fd, file.data(), file.size()) == (ssize_t)file.size();
+  const int wr = open(path, O_WRONLY);
+  unlink(path);
+  REQUIRE(written && wr >= 0);
+  {                                                                          // ends exactly at the end of the file
+    std::vector<unsigned char> dst(body);
+    REQUIRE(kmpiece::read_exact(fd, dst.data(), body, header) == 0);
+    REQUIRE(memcmp(dst.data(), file.data() + header, body) == 0);
+  }
+  {                                                                          // the second of three pieces of 32 bytes
+    std::vector<unsigned char> dst(32);
+    REQUIRE(kmpiece::read_exact(fd, dst.data(), 32, header + 32) == 0);
+    REQUIRE(memcmp(dst.data(), file.data() + header + 32, 32) == 0);
+  }
+  {                                                                          // nothing asked for: nothing touched
+    std::vector<unsigned char> dst(1, 0xA5);
+    REQUIRE(kmpiece::read_exact(fd, dst.data(), 0, header) == 0 && dst[0] == 0xA5);
+    REQUIRE(kmpiece::read_exact(fd, nullptr, 0, file.size() + 7) == 0);
+  }
+  {                                                                          // the file is one byte short
+    std::vector<unsigned char> dst(body, 0xA5);
+    REQUIRE(kmpiece::read_exact(fd, dst.data(), body, header + 1) == kmpiece::ENDED_EARLY);
+    REQUIRE(memcmp(dst.data(), file.data() + header + 1, body - 1) == 0 && dst[body - 1] == 0xA5);
+    REQUIRE(kmpiece::read_exact(fd, dst.data(), 1, file.size()) == kmpiece::ENDED_EARLY);
+  }
+  {                                                                          // a read that fails: its errno
+    std::vector<unsigned char> dst(body, 0xA5);
+    REQUIRE(kmpiece::read_exact(wr, dst.data(), body, header) == EBADF);
+    REQUIRE(dst[0] == 0xA5 && dst[body - 1] == 0xA5);
+  }
+  close(wr);
+  close(fd);
+  return 0;
+}
+
 int main() {
+  if (read_area()) return 1;
   const uint64_t stages[] = {256, 4096, 16ull << 20};
   for (uint64_t stage : stages) {
     for (uint64_t rec = 3; rec <= 12; ++rec)

@@ -184,6 +184,47 @@ def test_synthetic_files(tmp_path):
     assert kmlib.histo_kernel_ms() == 0.0
 
 
+@pytest.mark.parametrize("k, counter_len, sizes", [(21, 2, (32, 96, 97)), (31, 4, (21, 63, 64))])
+def test_where_a_piece_ends_with_the_buffer(tmp_path, monkeypatch, k, counter_len, sizes):
+    """256-byte staging.  k = 21 with 2 count bytes: records of 8 bytes, 32 to a piece, which fills the buffer to its
+    last byte; k = 31: records of 12 bytes, 21 to a piece, 252 of the 256 bytes.  Files of one full piece, of three,
+    and of three and one record more, through every user of the shared path: jf_histo of the file, add_jf of it twice
+    into a counter, histo(), finish(), write_jf, jf_histo of what was written; on a pool stream and on the caller's."""
+    monkeypatch.setenv("KM_COUNT_STAGE_BYTES", "256")
+    rng = np.random.default_rng(94)
+    assert 256 // ((2 * k + 7) // 8 + counter_len) == sizes[0]
+    stream = kmlib.stream_create()
+    try:
+        for n in sizes:
+            keys = distinct_keys(rng, n, k)
+            counts = rng.integers(1, 65536, n).astype(np.uint32)
+            counts[0], counts[-1] = 1, 65535
+            order = np.argsort(keys, kind="stable")
+            twice = (keys[order], counts[order] * np.uint32(2))
+            path = write_file(tmp_path / ("in_%d.jf" % n), keys, counts, k, canonical=False, counter_len=counter_len)
+            got = {}
+            for st in (None, stream):
+                first = kmlib.jf_histo(path, stream=st)
+                assert agree(first, model(counts)) and (first[2]["k"], first[2]["n_records"]) == (k, n), (n, st)
+                out = str(tmp_path / ("out_%d.jf" % n))
+                c = kmlib.Counter(k=k, canonical=False)
+                try:
+                    assert c.add_jf(path) == n and c.add_jf(path) == n
+                    assert agree(c.histo(), model(twice[1])), (n, st)
+                    c.finish().close()
+                    c.write_jf(out)
+                    assert tc.same(tc.sorted_records(c), twice), (n, st)
+                finally:
+                    c.close()
+                second = kmlib.jf_histo(out, stream=st)
+                assert agree(second, model(twice[1])) and (second[2]["k"], second[2]["n_records"]) == (k, n), (n, st)
+                got[st] = (first, second)
+            for a, b in zip(got[None], got[stream]):
+                assert np.array_equal(a[1], b[1]) and a[2] == b[2], n
+    finally:
+        kmlib.stream_destroy(stream)
+
+
 # ------------------------------------------------------------------ hot bins, cold bins, the edge of the LDS image
 @pytest.mark.parametrize("rounds", [None, "1", "2", "8"])                 # None: the depth compiled in, 0
 def test_hot_and_cold_bins_at_any_number_of_rounds(tmp_path, monkeypatch, rounds):

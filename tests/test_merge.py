@@ -183,7 +183,9 @@ def test_argument_errors_without_a_counter():
 
 def test_piece_arithmetic_under_the_sanitizers(tmp_path):
     """csrc/merge_pieces.h built for the CPU with AddressSanitizer + UBSan (tests/host/merge_pieces.cpp): record
-    sizes 3..12 at staging sizes of 256, 4 096 and 16 MiB, and host arrays packed into 12-byte records."""
+    sizes 3..12 at staging sizes of 256, 4 096 and 16 MiB, host arrays packed into 12-byte records, and read_exact
+    over a temporary file: to its last byte, from an odd offset, nothing, one byte too many, a descriptor that cannot
+    be read."""
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("no g++")

@@ -549,6 +549,49 @@ int km_histo_text(uint64_t base, uint64_t increment, const uint64_t* bins, uint6
                   uint64_t cap, uint64_t* len);
 int km_histo_stats_text(const km_histo_stats_t* stats, char* out, uint64_t cap, uint64_t* len);
 
+/* ---- dump and query: records as text ----------------------------------------------------------------
+ * What `jellyfish dump [-c [-t]] [-L lower] [-U upper]` and `jellyfish query` print, the text built on the device
+ * from records that are in HBM or streamed through it ("Dump and query").  The rule below is THIS
+ * PROJECT'S READING of the two commands, not checked against a run of Jellyfish: no Jellyfish binary was available.
+ *   KM_DUMP_FASTA   ">COUNT\nMER\n"     the default of `jellyfish dump`
+ *   KM_DUMP_COLUMN  "MER COUNT\n"       -c, and every line of `query`
+ *   KM_DUMP_TAB     "MER\tCOUNT\n"      -c -t
+ * MER: k letters, ACGT for 0..3, the first base from the most significant used bit pair (bits above 2k of a file's
+ * key bytes are ignored).  COUNT: decimal, no padding, "0" for zero.  A record is printed iff lower <= count <= upper
+ * (0 and 2^32 - 1 print all of them, a zero-count record of a file too; lower > upper prints nothing and is no error).
+ * Lines come in the order of the input: file order, the order of km_counter_records, query order.  Nothing is sorted.
+ * The longest line has k + 13 bytes. */
+#ifndef KM_DUMP_FASTA
+#define KM_DUMP_FASTA 0
+#define KM_DUMP_COLUMN 1
+#define KM_DUMP_TAB 2
+#endif
+/* records_in: records looked at; records_out: lines written; bytes_out: their bytes; pieces: how many pieces the
+ * records were cut into (a piece's text fits one staging buffer: KM_COUNT_STAGE_BYTES / (k + 13) records at most) */
+typedef struct { uint64_t records_in, records_out, bytes_out, pieces, reserved[4]; } km_dump_stats_t;
+
+/* Host arrays in, text into out[cap].  *len is always the length of the whole text; KM_E_CAPACITY, naming both
+ * numbers, if cap is smaller (out is then left untouched); out == NULL with cap 0 asks for *len only.  Before any
+ * device work: KM_E_ARG for null arguments, a format other than the three, device < 0, k outside 2..32. */
+int km_dump_text(int device, const uint64_t* keys, const uint32_t* counts, uint64_t n, int k, int format,
+                 uint32_t lower, uint32_t upper, char* out, uint64_t cap, uint64_t* len, void* stream);
+/* The record area of a binary/sorted file, read piece by piece as km_jf_histo reads it, as text to the descriptor
+ * out_fd (short writes and EINTR are handled; any other failure of write is KM_E_IO with the system's message, and
+ * nothing of the call is left running on the device).  Before any device work: KM_E_ARG as above, KM_E_IO for a
+ * descriptor that is not open, KM_E_IO / KM_E_FORMAT / KM_E_K for the file as kmjf_open gives them.  A file without
+ * records writes nothing.  stats may be NULL.  stream: a hipStream_t, NULL = one of the library's own. */
+int km_jf_dump(int device, const char* path, int out_fd, int format, uint32_t lower, uint32_t upper,
+               km_dump_stats_t* stats, void* stream);
+/* After km_counter_finish (KM_E_STATE before): the kept records, in the order of km_counter_records, straight out of
+ * HBM; the counter stays usable for km_counter_write_jf, km_counter_records and km_counter_histo. */
+int km_counter_dump(km_counter_t* c, int out_fd, int format, uint32_t lower, uint32_t upper, km_dump_stats_t* stats);
+/* `query`: one KM_DUMP_COLUMN line per k-mer with its count in the uploaded table (KM_E_STATE without one), 0 for a
+ * k-mer that is not there, in the order given; duplicates repeat.  The k-mers are looked up and printed as they are
+ * given: for a canonical database the caller passes min(k-mer, reverse complement). */
+int kmjf_query_text(kmjf_t* h, const uint64_t* kmers, uint64_t n, int out_fd, km_dump_stats_t* stats, void* stream);
+/* the time of the sizes / scan / write kernels of the calling thread's last call of the four above, by HIP events */
+int km_dump_kernel_ms(float* ms);
+
 /* ---- measurement helpers (bench.py at N = 1 holds no device buffers of its own) ------------- */
 int km_device_sync(int device);                                    /* hipDeviceSynchronize on `device`          */
 /* device-to-device copy of `bytes` bytes, `reps` times: read + write GB/s (the box's large-copy

@@ -1,5 +1,5 @@
-"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, ``count``, ``merge``, ``histo``
-and ``stats``.
+"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, ``count``, ``merge``, ``histo``,
+``stats``, ``dump`` and ``query``.
 
 Same flags, same ``#key:value`` echo, same TSV and ``#Elapsed time`` trailer as
 km/tools/find_mutation.py:17-60 and km/argparser/find_mutation.py:4-58, so the
@@ -323,6 +323,8 @@ def main_count(args, err=None):
         err.write("#min_qual_char:%s\n" % args.min_qual_char)
     if not args.jellyfish_order:
         kc.write_records(args.output, keys, counts, args.mer_len, args.canonical, cmdline=cmdline)
+    if args.dump:                                       # of the file just written: its records in its order
+        kc.dump_file(args.output, out=args.dump, fmt="column", device=default_device())
 
 
 def main_merge(args, err=None):
@@ -352,6 +354,8 @@ def main_merge(args, err=None):
     err.write("#mode:%s\n" % mode)
     if not args.jellyfish_order:
         kc.write_records(args.output, keys, counts, stats["k"], stats["canonical"], cmdline=cmdline)
+    if args.dump:                                       # of the file just written: its records in its order
+        kc.dump_file(args.output, out=args.dump, fmt="column", device=default_device())
 
 
 def _write_text(text, path, out=None):
@@ -381,6 +385,33 @@ def main_stats(args, out=None):
     _, _, stats = kc.histo_file(args.db, lower_count=args.lower_count, upper_count=args.upper_count,
                                 device=default_device())
     _write_text(kc.format_stats(stats), args.output, out)
+
+
+def main_dump(args):
+    """`jellyfish dump [-c] [-t] [-L N] [-U N] [-o FILE] db.jf` on the GPU (km_amd.count.dump_file): the records of
+    the file in file order, ">COUNT" and MER on two lines, or "MER COUNT" with -c ("MER<tab>COUNT" with -c -t); -L / -U
+    print only the records with -L <= count <= -U.  The library writes straight to the output's descriptor.  This
+    project's reading of the command, not checked against a run of Jellyfish."""
+    from . import count as kc
+    from .lib import KmError
+    fmt = "fasta" if not args.column else "tab" if args.tab else "column"
+    try:
+        kc.dump_file(args.db, out=args.output, fmt=fmt, lower_count=args.lower_count, upper_count=args.upper_count,
+                     device=default_device())
+    except KmError as e:
+        sys.exit("ERROR: dump: %s" % e)
+
+
+def main_query(args):
+    """`jellyfish query [-s FILE]... [-o FILE] db.jf [MER ...]` on the GPU (km_amd.count.query_file): "MER COUNT" per
+    k-mer, the k-mers of the -s FASTA files first, then the MER arguments; the canonical k-mer for a canonical
+    database.  This project's reading of the command, not checked against a run of Jellyfish."""
+    from . import count as kc
+    from .lib import KmError
+    try:
+        kc.query_file(args.db, mers=args.mers, seq_files=args.sequence, out=args.output, device=default_device())
+    except KmError as e:
+        sys.exit("ERROR: query: %s" % e)
 
 
 def _count_value(text):
@@ -439,6 +470,8 @@ def build_parser():
                          "parsed on the GPU; no effect on FASTA)")
     ct.add_argument("--histo", metavar="FILE", default=None,
                     help="also write the histogram of the counts written (after -L), as `histo OUT` prints it")
+    ct.add_argument("--dump", metavar="FILE", default=None,
+                    help="also write the records written (after -L) as text: byte for byte what `dump -c OUT` prints")
     ct.add_argument("reads", nargs="+", help="FASTA or FASTQ files, plain or gzip; - is stdin")
     mg = sub.add_parser("merge", help="sum (or --max) the counts of several .jf files of one k on the GPU -> one .jf")
     mg.add_argument("-L", "--lower-count", type=int, default=1, help="don't output k-mers with a merged count < lower-count")
@@ -448,6 +481,8 @@ def build_parser():
                     help="write the records in Jellyfish's own order (matrix position, then key), sorted on the GPU")
     mg.add_argument("--histo", metavar="FILE", default=None,
                     help="also write the histogram of the counts written (after -L), as `histo OUT` prints it")
+    mg.add_argument("--dump", metavar="FILE", default=None,
+                    help="also write the records written (after -L) as text: byte for byte what `dump -c OUT` prints")
     mg.add_argument("inputs", nargs="+", metavar="db.jf", help="binary/sorted files of one k and one canonical setting")
     hs = sub.add_parser("histo", add_help=False,
                         help="histogram of the counts of a .jf file, on the GPU (-h is --high as in Jellyfish: help is "
@@ -466,12 +501,37 @@ def build_parser():
     ss.add_argument("-U", "--upper-count", type=_count32, default=0xFFFFFFFF, help="ignore k-mers with count > upper-count")
     ss.add_argument("-o", "--output", default=None, help="output file (default: standard output)")
     ss.add_argument("db", metavar="db.jf", help="a binary/sorted file")
+    dp = sub.add_parser("dump", help="the k-mers and counts of a .jf file as text, built on the GPU")
+    dp.add_argument("-c", "--column", action="store_true", help="column format: MER COUNT on one line")
+    dp.add_argument("-t", "--tab", action="store_true", help="with -c: a tab between MER and COUNT")
+    dp.add_argument("-L", "--lower-count", type=_count32, default=0, help="don't print k-mers with count < lower-count")
+    dp.add_argument("-U", "--upper-count", type=_count32, default=0xFFFFFFFF, help="don't print k-mers with count > upper-count")
+    dp.add_argument("-o", "--output", default=None, help="output file (default: standard output)")
+    dp.add_argument("db", metavar="db.jf", help="a binary/sorted file")
+    qr = sub.add_parser("query", help="the counts of given k-mers in a .jf file, looked up and printed on the GPU")
+    qr.add_argument("-s", "--sequence", action="append", default=[], metavar="FILE",
+                    help="query every k-mer of this FASTA file (plain or gzip); may be given several times")
+    qr.add_argument("-o", "--output", default=None, help="output file (default: standard output)")
+    qr.add_argument("db", metavar="db.jf", help="a binary/sorted file")
+    qr.add_argument("mers", nargs="*", metavar="MER", help="k-mers of the file's k, letters of ACGT")
     return parser
+
+
+def parse_args(argv=None, parser=None):
+    """build_parser().parse_args plus what argparse cannot say on its own, refused the same way (exit status 2):
+    `dump -t` without `-c`, `query` with neither -s nor a MER."""
+    parser = build_parser() if parser is None else parser
+    args = parser.parse_args(argv)
+    if args._cmd == "dump" and args.tab and not args.column:
+        parser.error("dump: -t needs -c")
+    if args._cmd == "query" and not args.sequence and not args.mers:
+        parser.error("query: nothing to query: give -s FILE or MER arguments")
+    return args
 
 
 def main(argv=None):
     parser = build_parser()
-    args = parser.parse_args(argv)
+    args = parse_args(argv, parser)
     cmd = args._cmd
     del args._cmd
     # KM_DEVICES=0,1,..: one rank per listed GPU, started here (before anything touches a GPU)
@@ -496,6 +556,10 @@ def main(argv=None):
         main_histo(args)
     elif cmd == "stats":
         main_stats(args)
+    elif cmd == "dump":
+        main_dump(args)
+    elif cmd == "query":
+        main_query(args)
     else:
         parser.print_help(sys.stderr)
         sys.exit(1)

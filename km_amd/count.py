@@ -9,11 +9,15 @@ database built on the device from the counted records; ``write_records`` writes 
 framing the readers of this project load, sorted by key; ``write_jellyfish`` writes them in Jellyfish's own
 record order (sorted on the GPU), as ``Counter.write_jf`` does for records still on the device.
 ``histo_file``, ``format_histo`` and ``format_stats`` are behind ``python -m km_amd histo`` / ``stats``: the histogram
-of a file's counts and its four statistics in one pass on the GPU.  Only the standard library and numpy.
+of a file's counts and its four statistics in one pass on the GPU.  ``dump_file`` and ``query_file`` are behind
+``dump`` / ``query``: a file's records, or the counts of given k-mers, as text built on the GPU.  Only the standard
+library and numpy.
 """
 
+import contextlib
 import gzip
 import json
+import os
 import sys
 
 import numpy as np
@@ -155,6 +159,120 @@ def write_histo(counter, path):
     base, bins, _ = counter.histo()
     with open(path, "w") as fh:
         fh.write(format_histo(base, 1, bins))
+
+
+@contextlib.contextmanager
+def _text_out(out):
+    """The descriptor of `out`: a path (opened here; a file this call created is removed again if the block fails,
+    one that was there before is not), a file object with fileno() (flushed before its descriptor is handed over), or
+    None for standard output."""
+    if out is None:
+        out = sys.stdout
+    if isinstance(out, (str, bytes, os.PathLike)):
+        created = not os.path.exists(out)
+        fh = open(out, "wb")
+        try:
+            yield fh.fileno()
+        except BaseException:
+            fh.close()
+            if created:
+                with contextlib.suppress(OSError):
+                    os.remove(out)
+            raise
+        fh.close()
+    else:
+        yield _lib.out_descriptor(out)
+
+
+def dump_file(path, out=None, fmt="fasta", lower_count=0, upper_count=0xFFFFFFFF, device=0):
+    """What `jellyfish dump [-c [-t]] [-L lower_count] [-U upper_count] db.jf` prints: the records of a
+    `binary/sorted` file with lower_count <= count <= upper_count, in file order, as ">COUNT\nMER\n" ("fasta"),
+    "MER COUNT\n" ("column") or "MER\tCOUNT\n" ("tab").  The records stream through the GPU piece by piece and the
+    text is built there (lib.jf_dump); the host only writes it.  `out`: a path, a file object with fileno(), or None
+    for standard output -> the dict of km_dump_stats_t.  This project's reading of the command, not checked against a
+    run of Jellyfish."""
+    _lib.jf_file_info(path)                               # a missing or foreign input fails before `out` is opened
+    with _text_out(out) as fd:
+        return _lib.jf_dump(path, fd, fmt=fmt, lower_count=lower_count, upper_count=upper_count, device=device)
+
+
+_BASE_CODE = np.full(256, 4, np.uint8)
+for _i, _c in enumerate(b"ACGT"):
+    _BASE_CODE[_c] = _BASE_CODE[_c + 32] = _i
+
+
+def check_mers(mers, k):
+    """Every MER argument of `query` has exactly k letters of ACGTacgt, else SystemExit naming it and its position."""
+    for pos, mer in enumerate(mers, 1):
+        text = mer if isinstance(mer, str) else bytes(mer).decode("latin-1")
+        if len(text) != k or any(ch not in "ACGTacgt" for ch in text):
+            raise SystemExit("ERROR: query: MER argument %d (%r) is not %d letters of ACGT" % (pos, text, k))
+
+
+def _fasta_records(path):
+    """The sequences of a FASTA file (plain or gzip), the lines of a record joined, as uint8 arrays."""
+    fh, close = _open(path)
+    try:
+        lines = None
+        for line in fh:
+            if line.startswith(b">"):
+                if lines is not None:
+                    yield np.frombuffer(b"".join(lines), np.uint8)
+                lines = []
+            elif lines is not None:
+                lines.append(line.strip())
+        if lines is not None:
+            yield np.frombuffer(b"".join(lines), np.uint8)
+    finally:
+        if close:
+            fh.close()
+
+
+def _windows(seq, k):
+    """The packed k-mers of all windows of `seq` (uint8 text) in order; a window with a non-ACGT byte is skipped."""
+    if seq.size < k:
+        return np.zeros(0, np.uint64)
+    codes = _BASE_CODE[seq]
+    n = seq.size - k + 1
+    keys = np.zeros(n, np.uint64)
+    for j in range(k):                                   # k vectorised steps: the stated limit of `query -s`
+        keys = (keys << np.uint64(2)) | (codes[j:j + n] & 3).astype(np.uint64)
+    bad = np.concatenate(([0], np.cumsum(codes == 4)))
+    return keys[bad[k:] == bad[:-k]]
+
+
+def query_keys(k, canonical, mers=(), seq_files=()):
+    """The key array `query` looks up, on the host: every k window of every record of the `seq_files` (FASTA), in the
+    order given, then the `mers`; for a canonical database every key is min(key, reverse complement)."""
+    from . import kmer as km
+    check_mers(mers, k)
+    parts = [_windows(seq, k) for path in seq_files for seq in _fasta_records(path)]
+    if mers:
+        text = "".join(m if isinstance(m, str) else bytes(m).decode("latin-1") for m in mers)
+        # (the mers end to end, each checked above: every k-th window of that text is one of them)
+        parts.append(_windows(np.frombuffer(text.encode("latin-1"), np.uint8), k)[::k])
+    keys = np.concatenate(parts) if parts else np.zeros(0, np.uint64)
+    if canonical and keys.size:
+        keys = np.minimum(keys, km.revcomp(keys, k))
+    return np.ascontiguousarray(keys, np.uint64)
+
+
+def query_file(db_path, mers=(), seq_files=(), out=None, device=0):
+    """What `jellyfish query db.jf [-s FILE]... [MER ...]` prints: "MER COUNT" per k-mer, 0 for one that is not in
+    the table; the windows of the -s files first, in the order given, then the MER arguments.  For a canonical database
+    the canonical k-mer is looked up and printed.  Lookups and text are made on the GPU (Database.query_text); the
+    k-mers of the -s files are extracted on the host with numpy -> the dict of km_dump_stats_t.  This project's reading
+    of the command, not checked against a run of Jellyfish."""
+    info = _lib.jf_file_info(db_path)
+    check_mers(mers, info["k"])                           # before the table is loaded
+    keys = query_keys(info["k"], info["canonical"], mers=mers, seq_files=seq_files)
+    db = _lib.Database.open(db_path)
+    try:
+        db.upload(device)
+        with _text_out(out) as fd:
+            return db.query_text(keys, fd)
+    finally:
+        db.close()
 
 
 def write_records(path, keys, counts, k, canonical, cmdline=None):

@@ -17,6 +17,8 @@
 //                  on the counter's staging
 //   histo_host.h   km_histo_*, km_counter_histo, km_jf_histo: the count histogram and the four statistics of a counter
 //                  or a file in one streaming pass (a file: RecordFile, a Staging of the call's own, CallStream)
+//   dump_host.h    km_dump_text, km_jf_dump, km_counter_dump, kmjf_query_text: records as the text of `dump` / `query`,
+//                  formatted on the device piece by piece and written to a descriptor (a Staging in, a Staging out)
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
 #include <hip/hip_runtime.h>
@@ -42,6 +44,8 @@
 #include "count_kernel.h"
 #include "deliver_kernel.h"
 #include "device_common.h"
+#include "dump_kernel.h"
+#include "dump_text.h"
 #include "fastq_cut.h"
 #include "fastq_kernel.h"
 #include "fastx_strip.h"
@@ -68,3 +72,4 @@ using namespace kmd;
 #include "jf_order_host.h"
 #include "merge_host.h"
 #include "histo_host.h"
+#include "dump_host.h"

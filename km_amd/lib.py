@@ -42,6 +42,7 @@ SYMBOLS = [
     "km_counter_write_jf",
     "km_jf_file_info", "km_counter_add_records", "km_counter_add_jf", "km_counter_merge_stats",
     "km_histo_layout", "km_counter_histo", "km_jf_histo", "km_histo_kernel_ms", "km_histo_text", "km_histo_stats_text",
+    "km_dump_text", "km_jf_dump", "km_counter_dump", "kmjf_query_text", "km_dump_kernel_ms",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
 ]
 
@@ -81,6 +82,12 @@ class HistoStats(C.Structure):
     """km_histo_stats_t (include/kmgpu.h)."""
     _fields_ = [("unique", C.c_uint64), ("distinct", C.c_uint64), ("total", C.c_uint64), ("max_count", C.c_uint64),
                 ("reserved", C.c_uint64 * 2)]
+
+
+class DumpStats(C.Structure):
+    """km_dump_stats_t (include/kmgpu.h)."""
+    _fields_ = [("records_in", C.c_uint64), ("records_out", C.c_uint64), ("bytes_out", C.c_uint64),
+                ("pieces", C.c_uint64), ("reserved", C.c_uint64 * 4)]
 
 
 class TextState(C.Structure):
@@ -258,6 +265,11 @@ def load():
         "km_histo_kernel_ms": [C.POINTER(C.c_float)],
         "km_histo_text": [u64, u64, vp, u64, i32, vp, u64, C.POINTER(u64)],
         "km_histo_stats_text": [C.POINTER(HistoStats), vp, u64, C.POINTER(u64)],
+        "km_dump_text": [i32, vp, vp, u64, i32, i32, u32, u32, vp, u64, C.POINTER(u64), vp],
+        "km_jf_dump": [i32, cp, i32, i32, u32, u32, C.POINTER(DumpStats), vp],
+        "km_counter_dump": [vp, i32, i32, u32, u32, C.POINTER(DumpStats)],
+        "kmjf_query_text": [vp, vp, u64, i32, C.POINTER(DumpStats), vp],
+        "km_dump_kernel_ms": [C.POINTER(C.c_float)],
         "km_device_count": [C.POINTER(i32)],
         "km_device_sync": [i32],
         "km_device_copy_GBs": [i32, u64, i32, C.POINTER(dbl)],
@@ -453,6 +465,16 @@ class Database:
                                             ptr(counts4)))
         return mask, counts4
 
+    def query_text(self, kmers, out_fd, stream=None):
+        """kmjf_query_text: one "MER COUNT" line per k-mer (uint64, as given: canonicalised by the caller for a
+        canonical database) to the descriptor out_fd, in the order given, 0 for an absent k-mer; the lookups and
+        the text are made on the device -> the dict of km_dump_stats_t."""
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        st = DumpStats()
+        check(self._lib.kmjf_query_text(self._h, ptr(kmers) if kmers.size else None, kmers.size, out_descriptor(out_fd),
+                                        C.byref(st), C.c_void_p(stream or 0)))
+        return _dump_stats_dict(st)
+
 
 def _byte_view(data):
     """A C-contiguous uint8 view of a bytes-like object (no copy for bytes, bytearray, memoryview, numpy)."""
@@ -613,6 +635,15 @@ class Counter:
                                          int(upper_count), ptr(bins), bins.size, C.byref(st)))
         return base, bins, _histo_stats_dict(st)
 
+    def dump(self, out, fmt="fasta", lower_count=0, upper_count=0xFFFFFFFF):
+        """km_counter_dump: the finished counter's records with lower_count <= count <= upper_count as text to `out`
+        (a descriptor, or a file object, which is flushed first), in the order of records(), formatted on the device
+        -> the dict of km_dump_stats_t."""
+        st = DumpStats()
+        check(self._lib.km_counter_dump(self._c, out_descriptor(out), _dump_format(fmt), int(lower_count), int(upper_count),
+                                        C.byref(st)))
+        return _dump_stats_dict(st)
+
 
 def _histo_stats_dict(st):
     return {"unique": int(st.unique), "distinct": int(st.distinct), "total": int(st.total),
@@ -668,6 +699,61 @@ def histo_stats_text(stats):
     out = np.zeros(max(ln.value, 1), np.uint8)
     check(lib.km_histo_stats_text(C.byref(st), ptr(out), out.size, C.byref(ln)))
     return out[:ln.value].tobytes().decode("ascii")
+
+
+DUMP_FORMATS = {"fasta": 0, "column": 1, "tab": 2}         # KM_DUMP_FASTA, KM_DUMP_COLUMN, KM_DUMP_TAB
+
+
+def _dump_format(fmt):
+    """The library's code of "fasta" / "column" / "tab"; anything else goes through as an int for it to refuse."""
+    return DUMP_FORMATS[fmt] if fmt in DUMP_FORMATS else int(fmt)
+
+
+def out_descriptor(out):
+    """The descriptor the library writes to: `out` itself, or that of a file object, flushed before it is handed over
+    so that what Python buffered comes first."""
+    if isinstance(out, int):
+        return out
+    out.flush()
+    return out.fileno()
+
+
+def _dump_stats_dict(st):
+    return {"records_in": int(st.records_in), "records_out": int(st.records_out), "bytes_out": int(st.bytes_out),
+            "pieces": int(st.pieces)}
+
+
+def dump_text(keys, counts, k, fmt="fasta", lower_count=0, upper_count=0xFFFFFFFF, device=0):
+    """km_dump_text: the records (keys, counts) with lower_count <= count <= upper_count as the text of `dump`, in
+    the order given -> bytes.  fmt "fasta" is ">COUNT\nMER\n", "column" "MER COUNT\n", "tab" "MER\tCOUNT\n"
+    (include/kmgpu.h has the rule: this project's reading of `jellyfish dump`)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if keys.shape != counts.shape or keys.ndim != 1:
+        raise ValueError("keys and counts must be 1-d arrays of one length")
+    out = np.empty(max(keys.size * (max(int(k), 0) + 13), 1), np.uint8)          # the longest line is k + 13 bytes
+    ln = C.c_uint64()
+    check(load().km_dump_text(int(device), ptr(keys) if keys.size else None, ptr(counts) if counts.size else None,
+                              keys.size, int(k), _dump_format(fmt), int(lower_count), int(upper_count), ptr(out),
+                              out.size, C.byref(ln), None))
+    return out[:ln.value].tobytes()
+
+
+def jf_dump(path, out_fd, fmt="fasta", lower_count=0, upper_count=0xFFFFFFFF, device=0, stream=None):
+    """km_jf_dump: the records of a `binary/sorted` file as text to the descriptor out_fd, in file order, streamed
+    through the GPU piece by piece -> the dict of km_dump_stats_t."""
+    st = DumpStats()
+    check(load().km_jf_dump(int(device), os.fsencode(path), out_descriptor(out_fd), _dump_format(fmt), int(lower_count),
+                            int(upper_count), C.byref(st), C.c_void_p(stream or 0)))
+    return _dump_stats_dict(st)
+
+
+def dump_kernel_ms():
+    """km_dump_kernel_ms: the time of the text kernels of this thread's last dump_text / jf_dump / Counter.dump /
+    Database.query_text."""
+    ms = C.c_float()
+    check(load().km_dump_kernel_ms(C.byref(ms)))
+    return float(ms.value)
 
 
 MERGE_MODES = {"sum": 0, "max": 1}         # KM_MERGE_SUM, KM_MERGE_MAX

@@ -33,9 +33,14 @@ timed as wall time around calls that end in km_counter_stats (which waits for th
                rounds (*_kernel_ms_by_rounds, KM_HISTO_ROUNDS); and beside them the paths a user has today:
                Counter.records() + np.bincount (host_records_*) and Database.open(path).records() + np.bincount
                (host_open_*)
+  dump       - dump_file of the file write_jf wrote, column format, to /dev/null and to a file beside it: wall time,
+               best and all of --write-reps runs; the time of the text kernels by HIP events (km_dump_kernel_ms),
+               bytes_out, bytes/s, pieces; and beside it the path a user has today: Database.open(path).records() and
+               a vectorised numpy formatter that writes the same bytes to a file (host_dump_*; compared byte for byte
+               at the `cache` size only).  --only dump runs this group alone, after the counting it needs
 and km_device_copy_GBs of the same run for scale.
 
-usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31] [--write-reps 3] [--text-reps 3]
+usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31] [--write-reps 3] [--text-reps 3] [--only dump]
 """
 import argparse
 import json
@@ -221,6 +226,77 @@ def time_histo_file(path, device, reps):
             **best_all("host_open_s", host)}
 
 
+POW10 = 10 ** np.arange(1, 10, dtype=np.uint64)
+
+
+def host_dump_column(keys, counts, k, fh, chunk=1 << 20):
+    """`dump -c` on the host with numpy: "MER COUNT\n" per record into fh, a chunk of records at a time."""
+    shifts = (2 * (k - 1 - np.arange(k))).astype(np.uint64)
+    for lo in range(0, keys.size, chunk):
+        key, cnt = keys[lo:lo + chunk], counts[lo:lo + chunk].astype(np.uint64)
+        nd = np.searchsorted(POW10, cnt, side="right").astype(np.int64) + 1
+        end = np.cumsum(k + 2 + nd)
+        at = end - (k + 2 + nd)
+        out = np.empty(int(end[-1]), np.uint8)
+        out[at[:, None] + np.arange(k)[None, :]] = ACGT[((key[:, None] >> shifts[None, :]) & np.uint64(3)).astype(np.intp)]
+        out[at + k] = 32
+        for d in range(10):
+            has = nd > d
+            out[(end - 2 - d)[has]] = (48 + (cnt[has] // np.uint64(10 ** d)) % np.uint64(10)).astype(np.uint8)
+        out[end - 1] = 10
+        fh.write(out.tobytes())
+
+
+def time_dump_file(counter, k, reps, compare):
+    """The field group `dump`: the finished counter's file (Counter.write_jf), then dump_file of it in column format to
+    /dev/null and to a file beside it, against Database.open(path).records() + host_dump_column (the same bytes:
+    compared when `compare`)."""
+    tmp = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else tempfile.gettempdir()
+    path = os.path.join(tmp, "count_bench_%d_dump.jf" % os.getpid())
+    device = counter.device
+    out_path, host_path = path + ".dump.txt", path + ".host_dump.txt"
+    null, to_file, kernel, host, parts, st = [], [], [], [], None, None
+    try:
+        counter.write_jf(path)
+        for _ in range(reps):
+            with open(os.devnull, "wb") as fh:
+                t0 = time.perf_counter()
+                st = kc.dump_file(path, out=fh, fmt="column", device=device)
+                null.append(time.perf_counter() - t0)
+            kernel.append(kmlib.dump_kernel_ms())
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            kc.dump_file(path, out=out_path, fmt="column", device=device)
+            to_file.append(time.perf_counter() - t0)
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            db = kmlib.Database.open(path)
+            keys, counts = db.records()
+            db.close()
+            t1 = time.perf_counter()
+            with open(host_path, "wb") as fh:
+                host_dump_column(keys, counts, k, fh)
+            t2 = time.perf_counter()
+            host.append(t2 - t0)
+            if parts is None or host[-1] <= min(host):
+                parts = {"open_records_s": t1 - t0, "format_write_s": t2 - t1}
+        assert os.path.getsize(out_path) == os.path.getsize(host_path) == st["bytes_out"]
+        if compare:
+            with open(out_path, "rb") as a, open(host_path, "rb") as b:
+                assert a.read() == b.read()
+    finally:
+        for p in (path, out_path, host_path):
+            if os.path.exists(p):
+                os.unlink(p)
+    return {"dump": {
+        "reps": reps, "dir": tmp, "records": st["records_out"], "bytes_out": st["bytes_out"], "pieces": st["pieces"],
+        **best_all("null_s", null), **best_all("file_s", to_file), **best_all("kernel_ms", kernel),
+        "null_bytes_per_s": st["bytes_out"] / min(null), "file_bytes_per_s": st["bytes_out"] / min(to_file),
+        "kernel_bytes_per_s": st["bytes_out"] / (min(kernel) * 1e-3), "compared": bool(compare),
+        **best_all("host_dump_s", host), "host_dump_parts": parts,
+    }}
+
+
 def time_writers(counter, k, reps):
     """The field group of the two file writers on a finished counter (and, on the file they leave, histo_file)."""
     tmp = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else tempfile.gettempdir()
@@ -310,7 +386,7 @@ def time_merge(stream, k, device, reps):
     }}
 
 
-def run_size(name, k, device, rng, write_reps=3, text_reps=3):
+def run_size(name, k, device, rng, write_reps=3, text_reps=3, only=None):
     genome_len, n_reads, stage = SIZES[name]
     if stage:
         os.environ["KM_COUNT_STAGE_BYTES"] = str(stage)
@@ -328,12 +404,17 @@ def run_size(name, k, device, rng, write_reps=3, text_reps=3):
     sized.add_bases(stream)
     st = sized.stats()
     t_bases = time.perf_counter() - t0
-    histo = time_histo_table(sized, write_reps)
+    histo = time_histo_table(sized, write_reps) if not only else {}
     t0 = time.perf_counter()
     db = sized.finish(2)
     t_finish = time.perf_counter() - t0
     n_kept = int(db.info.n_records)
     db.close()
+    dump = time_dump_file(sized, k, write_reps, compare=name == "cache")
+    if only == "dump":
+        sized.close()
+        return {"reads": n_reads, "kmers": st["kmers"], "distinct": st["distinct"], "kept_at_L2": n_kept,
+                "staging_bytes": stage or 16 << 20, **dump}
     histo.update(time_histo_kept(sized, write_reps))
     writers, histo_file = time_writers(sized, k, write_reps)
     histo.update(histo_file)
@@ -354,6 +435,7 @@ def run_size(name, k, device, rng, write_reps=3, text_reps=3):
         **writers,
         **merged,
         "histo": histo,
+        **dump,
     }
 
 
@@ -364,14 +446,15 @@ def main():
     ap.add_argument("-k", type=int, default=31)
     ap.add_argument("--write-reps", type=int, default=3)
     ap.add_argument("--text-reps", type=int, default=3)
+    ap.add_argument("--only", choices=["dump"], default=None, help="this field group alone, after the counting it needs")
     args = ap.parse_args()
     kmlib.load()
     rng = np.random.default_rng(2026)
     out = {"tool": "count_bench", "k": args.k, "sizes": {}}
     for name in args.sizes.split(","):
-        out["sizes"][name] = run_size(name, args.k, args.device, rng, args.write_reps, args.text_reps)
+        out["sizes"][name] = run_size(name, args.k, args.device, rng, args.write_reps, args.text_reps, args.only)
     out["km_device_copy_GBs"] = kmlib.device_copy_GBs(args.device, 1 << 30, 10)
-    for size in out["sizes"].values():
+    for size in out["sizes"].values() if not args.only else ():
         size["histo"]["table_fraction_of_copy"] = size["histo"]["table_GBs"] / out["km_device_copy_GBs"]
     print(json.dumps(out))
 

@@ -500,6 +500,37 @@ int km_counter_add_jf(km_counter_t* c, const char* path, int mode, uint64_t* n_r
  * their kernels by HIP events on the counter's stream, 0 otherwise.  Either may be NULL. */
 int km_counter_merge_stats(km_counter_t* c, uint64_t* records_in, float* kernel_ms);
 
+/* ---- set operations over tables that already exist ---------------------------------------------------
+ * The opposite kind of merge ("Set operations").  Every call below that feeds records is ONE input,
+ * however many staging pieces it spans, and an input without records is an input too:
+ *   KM_SET_INTERSECT  the keys present, with count > 0, in every input; the count is the minimum over all their
+ *                     records (a key that repeats inside one input takes part with the minimum of its records there
+ *                     and still is one input);
+ *   KM_SET_SUBTRACT   the records of the FIRST input whose key occurs, with count > 0, in no later input; the count is
+ *                     the first input's, a key that repeats inside it summed with saturation as by KM_MERGE_SUM.
+ * A record with count 0 is absent: in a later input of subtract it removes nothing.  With one input both are filters.
+ * The first input claims slots and may grow the table; later inputs only look keys up, so the table never grows after
+ * the first, whatever its size.  The result depends neither on the order of the records nor on the piece size, and,
+ * inputs 2..N being interchangeable by definition, not on their order.  These are THIS PROJECT'S OWN definitions, not
+ * checked against a run of `jellyfish merge --min` or any other tool.
+ * State (each refusal before any device work, the counter left as it was): a counter that has taken text, FASTQ or
+ * sum / max records refuses the set calls, a counter that has taken a set call refuses those and the other operation
+ * (KM_E_STATE, km_last_error names which); KM_E_ARG for NULL arguments or an op other than the two.  km_counter_stats'
+ * distinct counts the keys of the first input; km_counter_merge_stats tallies the records and kernels of these calls
+ * too.  km_counter_histo of such a counter is refused (KM_E_STATE) until it has finished: its live table holds keys that
+ * do not survive.  km_counter_finish keeps lower_count <= count, as km_counter_finish_range with upper 2^32 - 1. */
+#define KM_SET_INTERSECT 0
+#define KM_SET_SUBTRACT 1
+/* n (key, count) pairs as one input, packed and enqueued as km_counter_add_records does; n == 0 is an empty input. */
+int km_counter_set_records(km_counter_t* c, const uint64_t* keys, const uint32_t* counts, uint64_t n, int op);
+/* The record area of a file as one input, read as km_counter_add_jf reads it, with its checks of the header and of k /
+ * canonical and their messages; *n_records (may be NULL): the records in the file. */
+int km_counter_set_jf(km_counter_t* c, const char* path, int op, uint64_t* n_records);
+/* km_counter_finish with a cut on both sides: keeps lower_count <= count <= upper_count (upper < lower keeps nothing
+ * and is no error).  For every counter: reads, sum / max records, set operations.  Everything after finish
+ * (km_counter_records, km_counter_write_jf, km_counter_histo, km_counter_dump) works on what was kept. */
+int km_counter_finish_range(km_counter_t* c, uint32_t lower_count, uint32_t upper_count, kmjf_t** out);
+
 /* ---- histogram of counts and table statistics -----------------------------------------------------
  * What `jellyfish histo` and `jellyfish stats` print, from counts that are already in HBM or from a file streamed
  * through it ("Histogram and statistics").  Both definitions are THIS PROJECT'S READING of the two

@@ -329,15 +329,21 @@ def main_count(args, err=None):
 
 def main_merge(args, err=None):
     """Several .jf files of one k into one on the GPU (km_amd.count.merge_files): per k-mer the counts are summed
-    (saturating at 2^32 - 1) or, with --max, their maximum is kept; the records of the result with count >= -L are
-    written to OUT as `count` writes them (sorted by key, or Jellyfish's own order with --jellyfish-order).  With
-    one input it is a filter and re-writer.  This project's own semantics, not checked against `jellyfish merge`."""
+    (saturating at 2^32 - 1) or, with --max, their maximum is kept; --min keeps the k-mers that every input holds, with
+    their minimum count, --subtract the records of the first input whose k-mer no later input holds.  The records of
+    the result with -L <= count <= -U are written to OUT as `count` writes them (sorted by key, or Jellyfish's own
+    order with --jellyfish-order).  With one input it is a filter and re-writer.  This project's own semantics, not
+    checked against `jellyfish merge`."""
     err = sys.stderr if err is None else err
     from . import count as kc
-    mode = "max" if args.max else "sum"
-    db, stats, counter = kc.merge_files(args.inputs, mode=mode, lower_count=args.lower_count, device=default_device(),
-                                        keep_counter=True)
-    cmdline = ["km_amd", "merge", "-L", str(args.lower_count)] + (["--max"] if args.max else []) + (
+    mode = "max" if args.max else "intersect" if args.min else "subtract" if args.subtract else "sum"
+    upper = 0xFFFFFFFF if args.upper_count is None else args.upper_count
+    db, stats, counter = kc.merge_files(args.inputs, mode=mode, lower_count=args.lower_count, upper_count=upper,
+                                        device=default_device(), keep_counter=True)
+    # (-U is named only when given: a file written by an invocation without it keeps its bytes)
+    cmdline = ["km_amd", "merge", "-L", str(args.lower_count)] + (
+        ["-U", str(args.upper_count)] if args.upper_count is not None else []) + (["--max"] if args.max else []) + (
+        ["--min"] if args.min else []) + (["--subtract"] if args.subtract else []) + (
         ["--jellyfish-order"] if args.jellyfish_order else []) + ["-o", args.output] + list(args.inputs)
     try:
         if args.jellyfish_order:
@@ -352,6 +358,8 @@ def main_merge(args, err=None):
     for key in ("distinct", "slots", "n_grow", "records_in"):
         err.write("#%s:%d\n" % (key, stats[key]))
     err.write("#mode:%s\n" % mode)
+    if mode in ("intersect", "subtract"):
+        err.write("#records_out:%d\n" % stats["records_out"])
     if not args.jellyfish_order:
         kc.write_records(args.output, keys, counts, stats["k"], stats["canonical"], cmdline=cmdline)
     if args.dump:                                       # of the file just written: its records in its order
@@ -473,9 +481,15 @@ def build_parser():
     ct.add_argument("--dump", metavar="FILE", default=None,
                     help="also write the records written (after -L) as text: byte for byte what `dump -c OUT` prints")
     ct.add_argument("reads", nargs="+", help="FASTA or FASTQ files, plain or gzip; - is stdin")
-    mg = sub.add_parser("merge", help="sum (or --max) the counts of several .jf files of one k on the GPU -> one .jf")
+    mg = sub.add_parser("merge", help="sum (or --max), intersect (--min) or --subtract several .jf files of one k on the GPU -> one .jf")
     mg.add_argument("-L", "--lower-count", type=int, default=1, help="don't output k-mers with a merged count < lower-count")
+    mg.add_argument("-U", "--upper-count", type=_count32, default=None,
+                    help="don't output k-mers with a merged count > upper-count (default: no upper cut)")
     mg.add_argument("--max", action="store_true", help="keep the maximum count per k-mer instead of the sum")
+    mg.add_argument("--min", action="store_true",
+                    help="intersect: keep the k-mers that every input holds, with their minimum count")
+    mg.add_argument("--subtract", action="store_true",
+                    help="keep the records of the first input whose k-mer no later input holds")
     mg.add_argument("-o", "--output", default="mer_counts_merged.jf", help="output file (default: mer_counts_merged.jf)")
     mg.add_argument("--jellyfish-order", action="store_true",
                     help="write the records in Jellyfish's own order (matrix position, then key), sorted on the GPU")
@@ -519,11 +533,14 @@ def build_parser():
 
 def parse_args(argv=None, parser=None):
     """build_parser().parse_args plus what argparse cannot say on its own, refused the same way (exit status 2):
-    `dump -t` without `-c`, `query` with neither -s nor a MER."""
+    `dump -t` without `-c`, `query` with neither -s nor a MER, `merge` with more than one of --max / --min /
+    --subtract."""
     parser = build_parser() if parser is None else parser
     args = parser.parse_args(argv)
     if args._cmd == "dump" and args.tab and not args.column:
         parser.error("dump: -t needs -c")
+    if args._cmd == "merge" and args.max + args.min + args.subtract > 1:
+        parser.error("merge: --max, --min and --subtract exclude each other")
     if args._cmd == "query" and not args.sequence and not args.mers:
         parser.error("query: nothing to query: give -s FILE or MER arguments")
     return args

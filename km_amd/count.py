@@ -1,8 +1,8 @@
 """Counting k-mers from read files on the GPU: what `jellyfish count -m k -C -L n -s size reads.fq` does in
 front of every km tool (``python -m km_amd count``).
 
-``merge_files`` sums (or takes the maximum of) the records of existing .jf files into one table on the GPU
-(``python -m km_amd merge``).
+``merge_files`` sums (or takes the maximum of) the records of existing .jf files into one table on the GPU, or
+intersects / subtracts them (``python -m km_amd merge``).
 
 ``count_files`` streams FASTA / FASTQ files (plain or gzip) through :class:`km_amd.lib.Counter` and returns the
 database built on the device from the counted records; ``write_records`` writes such records in the file
@@ -92,38 +92,48 @@ def count_files(paths, k=31, canonical=True, lower_count=1, device=0, expected_d
     return db, stats
 
 
-def merge_files(paths, mode="sum", lower_count=1, device=0, expected_distinct=0, keep_counter=False):
-    """Merge `binary/sorted` files of one k and one canonical setting into one table on the GPU: per key the counts
-    are summed (saturating at 2^32 - 1) or, with mode="max", their maximum is kept; lower_count cuts the RESULT
+def merge_files(paths, mode="sum", lower_count=1, device=0, expected_distinct=0, keep_counter=False,
+                upper_count=0xFFFFFFFF):
+    """Merge `binary/sorted` files of one k and one canonical setting into one table on the GPU.  Per key the counts
+    are summed (saturating at 2^32 - 1) or, with mode="max", their maximum is kept.  mode="intersect" keeps the keys
+    that every file holds (count > 0), with the minimum of their counts; mode="subtract" keeps the records of the
+    FIRST file whose key no later file holds (Counter.set_jf).  lower_count and upper_count cut the RESULT
     -> (Database, stats), with keep_counter=True (Database, stats, Counter) as count_files.  stats is
-    Counter.stats() before the cut plus k, canonical, mode and records_in (records taken with count > 0).
+    Counter.stats() before the cut plus k, canonical, mode, records_in (records taken with count > 0) and records_out
+    (records after the cuts).
 
     Every header is read first (lib.jf_file_info, no GPU): a file whose k or canonical differs from the first
     file's raises ValueError before a counter exists.  The table is sized from expected_distinct, or else from the
-    largest input's record count, and doubles when the union needs it to.  These are this project's own semantics
-    of "merge", not checked against a run of `jellyfish merge`."""
+    largest input's record count (sum, max), where it doubles when the union needs it to, or from the first file's
+    (intersect, subtract), whose keys are all the table ever holds.  These are this project's own semantics of
+    "merge", not checked against a run of `jellyfish merge`."""
     if isinstance(paths, (str, bytes)):
         paths = [paths]
     paths = list(paths)
     if not paths:
         raise ValueError("no input files")
-    if mode not in _lib.MERGE_MODES:
-        raise ValueError("mode %r is neither 'sum' nor 'max'" % (mode,))
+    if mode not in _lib.MERGE_MODES and mode not in _lib.SET_OPS:
+        raise ValueError("mode %r is none of 'sum', 'max', 'intersect', 'subtract'" % (mode,))
     infos = [_lib.jf_file_info(p) for p in paths]
     first = infos[0]
     for p, info in zip(paths, infos):
         if (info["k"], info["canonical"]) != (first["k"], first["canonical"]):
             raise ValueError("%s holds k=%d canonical=%s, but %s (the first file) holds k=%d canonical=%s" % (
                 p, info["k"], info["canonical"], paths[0], first["k"], first["canonical"]))
-    size = int(expected_distinct) or max(info["n_records"] for info in infos)
+    set_op = mode in _lib.SET_OPS
+    size = int(expected_distinct) or (first["n_records"] if set_op else max(info["n_records"] for info in infos))
     counter = _lib.Counter(k=first["k"], canonical=first["canonical"], device=device, expected_distinct=size)
     try:
         for p in paths:
-            counter.add_jf(p, mode=mode)
+            if set_op:
+                counter.set_jf(p, op=mode)
+            else:
+                counter.add_jf(p, mode=mode)
         stats = counter.stats()
         stats.update(k=first["k"], canonical=first["canonical"], mode=mode,
                      records_in=counter.merge_stats()["records_in"])
-        db = counter.finish(lower_count)
+        db = counter.finish(lower_count, upper_count)
+        stats["records_out"] = counter.n_records()
     except BaseException:
         counter.close()
         raise

@@ -33,6 +33,9 @@ const char* fastq_error_text(unsigned kind) {
 }
 }  // namespace
 
+// What a counter has been fed: text, FASTQ and sum / max records (plain), or the inputs of one set operation.
+enum { FEED_NONE = 0, FEED_PLAIN = 1, FEED_SET = 2 };
+
 struct km_counter {
   int device = 0, k = 0, canonical = 0;
   Stream st;                              // (declared first: destroyed last)
@@ -53,6 +56,9 @@ struct km_counter {
   unsigned long long fq_error = FQ_NO_ERROR;   // what the device found, once read: (stream offset << 8) | kind
   KernelSpans merge_spans;                // KM_COUNT_TIME_MERGE: around every piece's record kernel (merge_host.h)
   km_counter_stats_t last = {0, 0, 0, 0, 0, 0};
+  int feed = FEED_NONE;                   // what the counter has taken: the two kinds do not mix (setops_host.h)
+  int set_op = 0;                         // FEED_SET: KM_SET_INTERSECT / KM_SET_SUBTRACT
+  uint32_t set_inputs = 0;                // FEED_SET: inputs so far, the empty ones too
   DevBuf<uint64_t> out_keys;
   DevBuf<uint32_t> out_counts;
   uint64_t n_out = 0;
@@ -75,6 +81,15 @@ static int counter_usable(const km_counter* c) {
   return KM_OK;
 }
 
+// ... and every call that feeds text, FASTQ or sum / max records
+static int counter_takes_plain(const km_counter* c) {
+  KMCHK(counter_usable(c));
+  if (c->feed == FEED_SET)
+    return fail(KM_E_STATE, "counter holds the inputs of a set operation (%s): it takes no text, FASTQ or sum / max records",
+                c->set_op == KM_SET_INTERSECT ? "intersect" : "subtract");
+  return KM_OK;
+}
+
 // waits for everything enqueued
 static int counter_read_meta(km_counter* c, unsigned long long* m) {
   HIPCHK(hipMemcpyAsync(m, c->meta, CM_WORDS * 8, hipMemcpyDeviceToHost, c->st));
@@ -86,7 +101,7 @@ static int counter_read_meta(km_counter* c, unsigned long long* m) {
   }
   c->last.bases = m[CM_BASES];
   c->last.kmers = m[CM_KMERS];
-  c->last.distinct = m[CM_DISTINCT] + (m[CM_ALLT] ? 1 : 0);
+  c->last.distinct = m[CM_DISTINCT] + (m[CM_ALLT] || m[CM_ALLT_HAVE] ? 1 : 0);
   c->last.slots = c->slots;
   c->last.n_grow = c->n_grow;
   return KM_OK;
@@ -212,9 +227,10 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
 
 extern "C" int km_counter_add_bases(km_counter_t* c, const uint8_t* bytes, uint64_t n) {
   if (!c || (n && !bytes)) return fail(KM_E_ARG, "null argument");
-  KMCHK(counter_usable(c));
+  KMCHK(counter_takes_plain(c));
   if (n == 0) return KM_OK;
   HIPCHK(hipSetDevice(c->device));
+  c->feed = FEED_PLAIN;
   int rc = counter_append(c, bytes, n);
   const uint8_t brk = kmstrip::BREAK;                 // k-mers never span two calls
   if (rc == KM_OK) rc = counter_append(c, &brk, 1);
@@ -241,10 +257,11 @@ int strip_failed(const kmstrip::Result& r) {
 
 extern "C" int km_counter_add_text(km_counter_t* c, const char* text, uint64_t n, int final, uint64_t* consumed) {
   if (!c || !consumed || (n && !text)) return fail(KM_E_ARG, "null argument");
-  KMCHK(counter_usable(c));
+  KMCHK(counter_takes_plain(c));
   *consumed = 0;
   if (n == 0 && !final) return KM_OK;
   HIPCHK(hipSetDevice(c->device));
+  c->feed = FEED_PLAIN;
   CounterSink sink{c};
   const kmstrip::Result r = kmstrip::strip(&c->text, text, n, final, sink);
   *consumed = r.consumed;
@@ -307,12 +324,13 @@ extern "C" int km_counter_add_fastq(km_counter_t* c, const char* text, uint64_t 
                                     uint64_t* consumed) {
   if (!c || !consumed || (n && !text)) return fail(KM_E_ARG, "null argument");
   if (min_qual_char < 0 || min_qual_char > 255) return fail(KM_E_ARG, "min_qual_char %d outside 0..255", min_qual_char);
-  KMCHK(counter_usable(c));
+  KMCHK(counter_takes_plain(c));
   *consumed = 0;
   const uint64_t end = final ? n : kmcut::cut(text, n);
   if (end) {
     HIPCHK(hipSetDevice(c->device));
     KMCHK(fastq_prepare(c));
+    c->feed = FEED_PLAIN;
     KMCHK(counter_begin_pieces(c));
   }
   for (uint64_t pos = 0; pos < end;) {
@@ -368,8 +386,10 @@ extern "C" int km_counter_stats(km_counter_t* c, km_counter_stats_t* s) {
   return KM_OK;
 }
 
-extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t** out) {
-  if (!c || !out) return fail(KM_E_ARG, "null argument");
+// km_counter_finish / km_counter_finish_range: the slots that survived (every slot unless the counter holds a set
+// operation) with lower <= count <= upper into the record arrays, then the lookup table from those.  `ranged` = the
+// compaction of setops_kernel.h; without it, the one of count_kernel.h that km_counter_finish has always used.
+static int counter_finish_cut(km_counter* c, uint32_t lower_count, uint32_t upper_count, bool ranged, kmjf_t** out) {
   KMCHK(counter_usable(c));
   HIPCHK(hipSetDevice(c->device));
   int rc = counter_flush(c);
@@ -380,18 +400,26 @@ extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t**
   rc = c->out_keys.alloc(cap);
   if (rc == KM_OK) rc = c->out_counts.alloc(cap);
   if (rc != KM_OK) return rc;
+  const bool intersect = c->feed == FEED_SET && c->set_op == KM_SET_INTERSECT;
+  const uint32_t want = intersect ? c->set_inputs - 1 : 0;      // of the spare word (setops_kernel.h)
   HIPCHK(hipMemsetAsync(c->meta.p + CM_OUT, 0, 8, c->st));
-  hipLaunchKernelGGL(k_count_compact, dim3(grid_for(c->slots, 256)), dim3(256), 0, c->st, c->table.p, c->slots,
-                     lower_count, c->out_keys.p, c->out_counts.p, c->meta.p);
+  if (ranged)
+    hipLaunchKernelGGL(k_set_compact, dim3(grid_for(c->slots, 256)), dim3(256), 0, c->st, c->table.p, c->slots, want,
+                       intersect ? 1 : 0, lower_count, upper_count, c->out_keys.p, c->out_counts.p, c->meta.p);
+  else
+    hipLaunchKernelGGL(k_count_compact, dim3(grid_for(c->slots, 256)), dim3(256), 0, c->st, c->table.p, c->slots,
+                       lower_count, c->out_keys.p, c->out_counts.p, c->meta.p);
   HIPCHK(hipGetLastError());
   KMCHK(counter_read_meta(c, m));
   uint64_t n = m[CM_OUT];
   if (n > m[CM_DISTINCT]) return fail(KM_E_HIP, "compaction wrote %llu records for %llu keys", m[CM_OUT], m[CM_DISTINCT]);
-  if (m[CM_ALLT] && m[CM_ALLT] >= lower_count) {        // T^32 of a non-canonical k = 32 table (count_kernel.h)
+  // T^32 of a non-canonical k = 32 table (count_kernel.h; under a set operation its cells are those of setops_kernel.h)
+  const bool have = intersect ? m[CM_ALLT_HAVE] != 0 : m[CM_ALLT] != 0;
+  const uint32_t allt = intersect ? ~(uint32_t)m[CM_ALLT] : (uint32_t)std::min<unsigned long long>(m[CM_ALLT], 0xFFFFFFFFull);
+  if (have && m[CM_ALLT_MATCH] == want && allt >= lower_count && allt <= upper_count) {
     const uint64_t key = EMPTY;
-    const uint32_t cnt = (uint32_t)std::min<unsigned long long>(m[CM_ALLT], 0xFFFFFFFFull);
     HIPCHK(hipMemcpyAsync(c->out_keys.p + n, &key, 8, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(c->out_counts.p + n, &cnt, 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(c->out_counts.p + n, &allt, 4, hipMemcpyHostToDevice, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     ++n;
   }
@@ -406,6 +434,11 @@ extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t**
   c->finished = true;
   *out = h;
   return KM_OK;
+}
+
+extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t** out) {
+  if (!c || !out) return fail(KM_E_ARG, "null argument");
+  return counter_finish_cut(c, lower_count, 0xFFFFFFFFu, c->feed == FEED_SET, out);
 }
 
 extern "C" int km_counter_records(km_counter_t* c, uint64_t* keys, uint32_t* counts, uint64_t cap, uint64_t* n) {

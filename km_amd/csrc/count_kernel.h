@@ -6,6 +6,7 @@
 // brought in.  Empty key = ~0 (device_common.h: EMPTY).  That value is also the k-mer T^32 of a non-canonical
 // k = 32 table (in canonical mode T^32 is stored as A^32 = 0): it is counted in a cell of its own (CM_ALLT).
 // Counts are integers added with atomics: the final set of (key, count) does not depend on arrival order.
+// The slot's fourth word is 0 everywhere except under the set operations of setops_kernel.h.
 #pragma once
 #include "device_common.h"
 
@@ -23,8 +24,9 @@ constexpr uint32_t COUNT_PAD = 128;     // readable bytes behind a staged chunk 
 // cells of the counter's device meta block (u64 each)
 // (CM_FORMAT: fastq_kernel.h's smallest (stream offset << 8 | kind), ~0 while the text is well-formed)
 // (CM_RECORDS: merge_kernel.h's tally of the records taken; CM_BASES / CM_KMERS tally text only)
+// (CM_ALLT_HAVE / CM_ALLT_MATCH: setops_kernel.h's "claimed" and spare word of the key ~0, which has no slot)
 enum { CM_DISTINCT = 0, CM_BASES = 1, CM_KMERS = 2, CM_ALLT = 3, CM_ERROR = 4, CM_OUT = 5, CM_FORMAT = 6, CM_RECORDS = 7,
-       CM_WORDS = 8 };
+       CM_ALLT_HAVE = 8, CM_ALLT_MATCH = 9, CM_WORDS = 10 };
 
 __global__ void k_count_init(CountSlot* slots, uint64_t n_slots) {
   uint4* p = reinterpret_cast<uint4*>(slots);

@@ -15,6 +15,8 @@
 //   jf_order_host.h  km_jf_*, km_counter_write_jf: files in Jellyfish's own record order (out through the same Staging)
 //   merge_host.h   km_jf_file_info, km_counter_add_records, km_counter_add_jf: records of existing tables, as pieces
 //                  on the counter's staging
+//   setops_host.h  km_counter_set_records, km_counter_set_jf, km_counter_finish_range: intersect / subtract over the
+//                  inputs of one counter, as pieces on the counter's staging
 //   histo_host.h   km_histo_*, km_counter_histo, km_jf_histo: the count histogram and the four statistics of a counter
 //                  or a file in one streaming pass (a file: RecordFile, a Staging of the call's own, CallStream)
 //   dump_host.h    km_dump_text, km_jf_dump, km_counter_dump, kmjf_query_text: records as the text of `dump` / `query`,
@@ -59,6 +61,7 @@
 #include "merge_pieces.h"
 #include "table_kernels.h"
 #include "walk_kernel.h"
+#include "setops_kernel.h"      // (last: the kernels before it keep their places in the code object)
 
 using namespace kmd;
 
@@ -71,5 +74,6 @@ using namespace kmd;
 #include "count_host.h"
 #include "jf_order_host.h"
 #include "merge_host.h"
+#include "setops_host.h"
 #include "histo_host.h"
 #include "dump_host.h"

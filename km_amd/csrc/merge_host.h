@@ -9,7 +9,7 @@ namespace {
 // What every add_* checks first, in their order.
 int merge_check(const km_counter* c, int mode) {
   if (mode != KM_MERGE_SUM && mode != KM_MERGE_MAX) return fail(KM_E_ARG, "mode %d is neither KM_MERGE_SUM nor KM_MERGE_MAX", mode);
-  return counter_usable(c);
+  return counter_takes_plain(c);
 }
 
 // n records of kb + cb bytes; fill(dst, piece) writes piece.bytes bytes of them to a pinned buffer.
@@ -18,6 +18,7 @@ int merge_enqueue(km_counter* c, uint64_t n, uint32_t kb, uint32_t cb, int mode,
   const uint64_t rec = (uint64_t)kb + cb, per = kmpiece::per_piece(c->stg.bytes, rec);
   HIPCHK(hipSetDevice(c->device));
   KMCHK(counter_begin_pieces(c));
+  c->feed = FEED_PLAIN;
   const uint64_t pieces = kmpiece::n_pieces(n, per);
   for (uint64_t i = 0; i < pieces; ++i) {
     const kmpiece::Piece p = kmpiece::piece(n, per, rec, i);

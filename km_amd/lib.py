@@ -41,6 +41,7 @@ SYMBOLS = [
     "km_jf_matrix", "km_jf_sort_records", "km_jf_sort_stats", "km_jf_sort_kernel_ms", "km_jf_header",
     "km_counter_write_jf",
     "km_jf_file_info", "km_counter_add_records", "km_counter_add_jf", "km_counter_merge_stats",
+    "km_counter_set_records", "km_counter_set_jf", "km_counter_finish_range",
     "km_histo_layout", "km_counter_histo", "km_jf_histo", "km_histo_kernel_ms", "km_histo_text", "km_histo_stats_text",
     "km_dump_text", "km_jf_dump", "km_counter_dump", "kmjf_query_text", "km_dump_kernel_ms",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
@@ -258,6 +259,9 @@ def load():
         "km_counter_add_records": [vp, vp, vp, u64, i32],
         "km_counter_add_jf": [vp, cp, i32, C.POINTER(u64)],
         "km_counter_merge_stats": [vp, C.POINTER(u64), C.POINTER(C.c_float)],
+        "km_counter_set_records": [vp, vp, vp, u64, i32],
+        "km_counter_set_jf": [vp, cp, i32, C.POINTER(u64)],
+        "km_counter_finish_range": [vp, u32, u32, C.POINTER(vp)],
         "km_histo_layout": [u64, u64, u64, C.POINTER(u64), C.POINTER(u64)],
         "km_counter_histo": [vp, u64, u64, u64, u32, u32, vp, u64, C.POINTER(HistoStats)],
         "km_jf_histo": [i32, cp, u64, u64, u64, u32, u32, vp, u64, C.POINTER(HistoStats), C.POINTER(C.c_int32),
@@ -587,9 +591,29 @@ class Counter:
         check(self._lib.km_counter_add_jf(self._c, os.fsencode(path), _merge_mode(mode), C.byref(n)))
         return int(n.value)
 
+    def set_records(self, keys, counts, op="intersect"):
+        """km_counter_set_records: (key, count) pairs as ONE input of a set operation over the counter's inputs.
+        "intersect": the keys with count > 0 in every input, with the minimum over all their records; "subtract": the
+        records of the first input whose key is, with count > 0, in no later one.  Pairs with count 0 are absent, keys
+        may repeat (one input all the same), an empty call is an empty input.  This project's own definitions."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        if keys.shape != counts.shape or keys.ndim != 1:
+            raise ValueError("keys and counts must be 1-d arrays of one length")
+        check(self._lib.km_counter_set_records(self._c, ptr(keys) if keys.size else None,
+                                               ptr(counts) if counts.size else None, keys.size, _set_op(op)))
+
+    def set_jf(self, path, op="intersect"):
+        """km_counter_set_jf: the records of a `binary/sorted` file of the counter's k and canonical as one input of
+        the set operation, as by set_records; returns the number of records in the file."""
+        n = C.c_uint64()
+        check(self._lib.km_counter_set_jf(self._c, os.fsencode(path), _set_op(op), C.byref(n)))
+        return int(n.value)
+
     def merge_stats(self):
         """km_counter_merge_stats (waits for everything added so far): dict(records_in = records with count > 0
-        taken by add_records / add_jf, kernel_ms = the time of their kernels, needs KM_COUNT_TIME_MERGE=1)."""
+        taken by add_records / add_jf / set_records / set_jf, kernel_ms = the time of their kernels, needs
+        KM_COUNT_TIME_MERGE=1)."""
         n, ms = C.c_uint64(), C.c_float()
         check(self._lib.km_counter_merge_stats(self._c, C.byref(n), C.byref(ms)))
         return {"records_in": int(n.value), "kernel_ms": float(ms.value)}
@@ -601,11 +625,22 @@ class Counter:
         return {"bases": int(s.bases), "kmers": int(s.kmers), "distinct": int(s.distinct), "slots": int(s.slots),
                 "n_grow": int(s.n_grow)}
 
-    def finish(self, lower_count=1):
-        """Keep the k-mers with count >= lower_count and build the lookup table from them -> Database."""
+    def finish(self, lower_count=1, upper_count=0xFFFFFFFF):
+        """Keep the k-mers with lower_count <= count <= upper_count (of a set operation: those that survived it) and
+        build the lookup table from them -> Database.  Without an upper cut this is km_counter_finish, with one
+        km_counter_finish_range."""
         h = C.c_void_p()
-        check(self._lib.km_counter_finish(self._c, int(lower_count), C.byref(h)))
+        if int(upper_count) == 0xFFFFFFFF:
+            check(self._lib.km_counter_finish(self._c, int(lower_count), C.byref(h)))
+        else:
+            check(self._lib.km_counter_finish_range(self._c, int(lower_count), int(upper_count), C.byref(h)))
         return Database(h)
+
+    def n_records(self):
+        """How many records the finished counter kept."""
+        n = C.c_uint64()
+        check(self._lib.km_counter_records(self._c, None, None, 0, C.byref(n)))
+        return int(n.value)
 
     def records(self):
         """(keys, counts) of the finished counter, as compacted on the device: in no particular order."""
@@ -762,6 +797,14 @@ MERGE_MODES = {"sum": 0, "max": 1}         # KM_MERGE_SUM, KM_MERGE_MAX
 def _merge_mode(mode):
     """The library's code of "sum" / "max"; anything else goes through as an int for the library to refuse."""
     return MERGE_MODES[mode] if mode in MERGE_MODES else int(mode)
+
+
+SET_OPS = {"intersect": 0, "subtract": 1}   # KM_SET_INTERSECT, KM_SET_SUBTRACT
+
+
+def _set_op(op):
+    """The library's code of "intersect" / "subtract"; anything else goes through as an int for it to refuse."""
+    return SET_OPS[op] if op in SET_OPS else int(op)
 
 
 def jf_file_info(path):

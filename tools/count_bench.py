@@ -24,7 +24,9 @@ timed as wall time around calls that end in km_counter_stats (which waits for th
                Counter.add_jf of both into a counter sized as merge_files sizes it: wall time to km_counter_stats,
                input records/s, the time of the record kernel by HIP events (KM_COUNT_TIME_MERGE), best and all of
                --write-reps runs; and beside it the host path a user has today: Database.open(..).records() of both
-               files combined with np.unique + np.add.at (host_merge_*)
+               files combined with np.unique + np.add.at (host_merge_*); and set_ops: sum, intersect and subtract
+               over the same two files, the record kernels of each input on their own (Counter.set_jf; --only merge
+               runs this group alone, without the host path)
   histo      - the count histogram and the four statistics (Counter.histo, default layout): wall time and the time of
                its kernel by HIP events (km_histo_kernel_ms), best and all of --write-reps runs, on the full counting
                table before finish (table_*: a stream read of 16 * slots bytes, also given as GB/s and as a fraction
@@ -40,7 +42,7 @@ timed as wall time around calls that end in km_counter_stats (which waits for th
                at the `cache` size only).  --only dump runs this group alone, after the counting it needs
 and km_device_copy_GBs of the same run for scale.
 
-usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31] [--write-reps 3] [--text-reps 3] [--only dump]
+usage: count_bench.py [--device 0] [--sizes cache,hbm] [-k 31] [--write-reps 3] [--text-reps 3] [--only dump|merge]
 """
 import argparse
 import json
@@ -333,8 +335,34 @@ def time_writers(counter, k, reps):
     }, histo_file
 
 
-def time_merge(stream, k, device, reps):
-    """The field group of merging: two files from the halves of the reads, add_jf of both against the host path."""
+def time_set_ops(paths, n_in, k, device, reps):
+    """sum, intersect and subtract over the same two files, each input's kernels timed on their own (merge_stats waits
+    for the device between the inputs, so the wall time of these runs is not that of add_jf_s)."""
+    out = {}
+    for mode in ("sum", "intersect", "subtract"):
+        per_input, kept = [], None
+        for _ in range(reps):
+            c = kmlib.Counter(k=k, device=device, expected_distinct=max(n_in) if mode == "sum" else n_in[0])
+            ms = [0.0]
+            for p in paths:
+                if mode == "sum":
+                    c.add_jf(p)
+                else:
+                    c.set_jf(p, op=mode)
+                ms.append(c.merge_stats()["kernel_ms"])
+            per_input.append([b - a for a, b in zip(ms, ms[1:])])
+            st = c.stats()
+            c.finish(1).close()
+            kept = c.n_records()
+            c.close()
+        out[mode] = {"kernel_ms_per_input_all": per_input, "kernel_ms_per_input": [min(r[i] for r in per_input) for i in (0, 1)],
+                     "records_out": kept, "table_slots": st["slots"], "n_grow": st["n_grow"]}
+    return out
+
+
+def time_merge(stream, k, device, reps, host_path=True):
+    """The field group of merging: two files from the halves of the reads, add_jf of both against the host path; then
+    the set operations over the same two files (time_set_ops)."""
     os.environ["KM_COUNT_TIME_MERGE"] = "1"
     tmp = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else tempfile.gettempdir()
     paths = [os.path.join(tmp, "count_bench_%d_half%d.jf" % (os.getpid(), i)) for i in range(2)]
@@ -358,7 +386,8 @@ def time_merge(stream, k, device, reps):
             wall.append(time.perf_counter() - t0)
             kernel.append(c.merge_stats()["kernel_ms"])
             c.close()
-        for _ in range(reps):
+        set_ops = time_set_ops(paths, n_in, k, device, reps)
+        for _ in range(reps if host_path else 0):
             t0 = time.perf_counter()
             recs = []
             for p in paths:
@@ -373,7 +402,7 @@ def time_merge(stream, k, device, reps):
             host.append(t2 - t0)
             if parts is None or host[-1] <= min(host):
                 parts = {"open_records_s": t1 - t0, "unique_add_s": t2 - t1}
-        assert keys.size == st["distinct"]
+        assert not host_path or keys.size == st["distinct"]
     finally:
         for p in paths:
             if os.path.exists(p):
@@ -382,7 +411,8 @@ def time_merge(stream, k, device, reps):
         "reps": reps, "dir": tmp, "records_in": n_in, "distinct": st["distinct"], "n_grow": st["n_grow"],
         "table_slots": st["slots"], "add_jf_s": min(wall), "add_jf_s_all": wall,
         "add_jf_records_per_s": sum(n_in) / min(wall), "add_jf_kernel_ms": min(kernel), "add_jf_kernel_ms_all": kernel,
-        "host_merge_s": min(host), "host_merge_s_all": host, "host_merge_parts": parts,
+        "host_merge_s": min(host) if host else None, "host_merge_s_all": host, "host_merge_parts": parts,
+        "set_ops": set_ops,
     }}
 
 
@@ -398,6 +428,8 @@ def run_size(name, k, device, rng, write_reps=3, text_reps=3, only=None):
     warm.add_bases(stream[:1_000_000])
     warm.finish().close()
     warm.close()
+    if only == "merge":
+        return {"reads": n_reads, "staging_bytes": stage or 16 << 20, **time_merge(stream, k, device, write_reps, host_path=False)}
 
     sized = kmlib.Counter(k=k, device=device, expected_distinct=0 if stage else 2 * genome_len + stream.size // 20)
     t0 = time.perf_counter()
@@ -446,7 +478,8 @@ def main():
     ap.add_argument("-k", type=int, default=31)
     ap.add_argument("--write-reps", type=int, default=3)
     ap.add_argument("--text-reps", type=int, default=3)
-    ap.add_argument("--only", choices=["dump"], default=None, help="this field group alone, after the counting it needs")
+    ap.add_argument("--only", choices=["dump", "merge"], default=None,
+                    help="this field group alone, after the counting it needs (merge: without the host path)")
     args = ap.parse_args()
     kmlib.load()
     rng = np.random.default_rng(2026)

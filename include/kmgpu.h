@@ -246,9 +246,11 @@ int km_batch_set_targets_dev(km_batch_t* b, const uint8_t* d_bases, const uint64
 /* With KM_RUN_TIMED: record the STAGE boundaries only (walk start / end, graph end, delivery) — the walk stage as it
  * runs in production, without the two event records between its three kernels; km_batch_timings [3], [4], [5] are 0. */
 #define KM_RUN_TIMED_STAGES 512
-/* Kept for callers of round 2: a batch's kernels now ALWAYS run in `stream`, in order (the pass over the
- * unflagged targets, k_graph_pure, used to run beside k_dfs on a side stream unless this flag was given;
- * it follows k_dfs, inside the graph stage of km_batch_timings).  The flag changes nothing. */
+/* Every kernel alone: a batch's kernels always run in `stream`, in order, and by default the pass over the unflagged
+ * targets (k_graph_pure) runs as blocks of k_dfs's own launch (k_dfs_pure; rounds 2-3: beside k_dfs on a side stream).
+ * With this flag k_dfs and k_graph_pure are one launch each, k_graph_pure behind k_dfs and inside the graph stage of
+ * km_batch_timings — what per-kernel measurements want.  (The environment's KM_FUSE_PURE=0 selects the same two
+ * launches for every run.)  Results are the same either way. */
 #define KM_RUN_SERIAL 64
 /* Launch the kernels asynchronously on `stream` (no host synchronisation unless
  * a target overflows the fast tier, in which case the large-tier pass needs one). */
@@ -285,7 +287,9 @@ int km_batch_graph_log(km_batch_t* b, uint32_t* removed_ref_edges, uint32_t* non
  * with HIP events on the launch stream:
  * [0] walk stage (k_pack + k_seed + k_dfs), [1] graph stage, [2] walk + graph,
  * [3] k_seed, [4] k_pack, [5] k_dfs, [6] the delivery kernels (k_out_scan + k_out_pack),
- * [7] the device-to-host copy ([6], [7]: 0 unless the run carried KM_RUN_DELIVER). */
+ * [7] the device-to-host copy ([6], [7]: 0 unless the run carried KM_RUN_DELIVER).
+ * Without KM_RUN_SERIAL a walk + graph run launches k_dfs and k_graph_pure as one kernel: [0] and [5] then contain
+ * the pure-chain pass and [1] is that much shorter; with KM_RUN_SERIAL (or KM_FUSE_PURE=0) the pass counts in [1]. */
 int km_batch_timings(km_batch_t* b, float* ms8);
 
 /* ---- host reporting: replaces, for all targets of a fetched batch at once, the per-target

@@ -18,6 +18,7 @@ struct Knobs {
   uint32_t graph_grid = 0;      // KM_GRAPH_GRID: blocks of k_graph when the epilogue of k_dfs is on (tests: force the overflow path)
   bool speculate = true;        // KM_SPECULATE=0: k_dfs walks every chain one lookup after the other (results unchanged)
   bool dfs_grid_full = false;   // KM_DFS_GRID_FULL=1: one block of k_dfs per target of the batch, as before round 4
+  bool fuse_pure = true;        // KM_FUSE_PURE=0: k_dfs and k_graph_pure as two launches, as before round 6 (results unchanged)
 };
 Knobs read_knobs() {
   Knobs q;
@@ -35,6 +36,7 @@ Knobs read_knobs() {
   q.graph_grid = (uint32_t)std::max<long>(0, num("KM_GRAPH_GRID", 0));
   q.speculate = num("KM_SPECULATE", 1) != 0;
   q.dfs_grid_full = num("KM_DFS_GRID_FULL", 0) != 0;
+  q.fuse_pure = num("KM_FUSE_PURE", 1) != 0;
   return q;
 }
 const Knobs& knobs() {
@@ -731,6 +733,19 @@ static void launch_dfs(km_batch* b, hipStream_t st, const WalkArgs& wa) {
   else hipLaunchKernelGGL((k_dfs<false, 0>), dim3(grid), dim3(64), b->walk_lds, st, wa);
 }
 
+// k_dfs and k_graph_pure as ONE launch (graph_kernel.h: k_dfs_pure): k_dfs's blocks first, then one block per target
+// for the pure-chain pass, every block with k_dfs's LDS.  Only where that holds the pure-chain pass as well
+// (fuses_pure): its position table has the power of two >= 4 (n_ref + 2) slots, k_dfs's the one >= 4 n_ref, so for a
+// longest target of 511-512, 1 023-1 024, ... k-mers the pure pass needs MORE than the walk (10 384 against 9 712
+// bytes at 512) and one launch would cost the walk blocks LDS, i.e. resident waves: such a batch keeps two launches.
+static bool fuses_pure(const km_batch* b) { return b->pure_lds <= b->walk_lds; }
+static void launch_dfs_pure(km_batch* b, hipStream_t st, const WalkArgs& wa, const GraphArgs& ga) {
+  const uint32_t dfs_grid = b->hints.dfs_grid(b->n_targets);
+  const uint32_t lds = b->walk_lds;
+  if (wa.tab.k == 31) hipLaunchKernelGGL((k_dfs_pure<31>), dim3(dfs_grid + b->n_targets), dim3(64), lds, st, wa, ga, dfs_grid);
+  else hipLaunchKernelGGL((k_dfs_pure<0>), dim3(dfs_grid + b->n_targets), dim3(64), lds, st, wa, ga, dfs_grid);
+}
+
 // Compaction kernels + ONE asynchronous copy of region A and the expected part of the tail into
 // the pinned twin; km_batch_result() waits for ev_out and fetches what the guess left behind.
 static int enqueue_deliver(km_batch* b, hipStream_t st, bool lean, bool count16 = false) {
@@ -904,10 +919,12 @@ struct RunFlags {
         count_fetches(s & KM_RUN_COUNT_FETCHES), timed(s & KM_RUN_TIMED), timed_fine(timed && !(s & KM_RUN_TIMED_STAGES)) {}
 };
 
-// One step.  In stream order: k_pack (which also zeroes the path-pool counters), k_seed, k_dfs, [k_dfs of the device's
-// large tier], k_graph_pure, k_graph, [k_graph of the device's large tier], then the delivery (enqueue_deliver) when
-// asked for; with KM_RUN_HIPGRAPH everything before the delivery is captured once and replayed.  A graph-only run
-// (no k_pack) zeroes the counters with a fill command of its own (launch_graph_fast).
+// One step.  In stream order: k_pack (which also zeroes the path-pool counters), k_seed, k_dfs_pure (k_dfs and
+// k_graph_pure in one launch), [k_dfs of the device's large tier], k_graph, [k_graph of the device's large tier], then
+// the delivery (enqueue_deliver) when asked for.  With KM_RUN_SERIAL ("every kernel alone"), KM_FUSE_PURE=0, a
+// walk-only run or the k_dfs diagnostics: k_dfs, [large-tier k_dfs], k_graph_pure, k_graph, ... as before round 6.
+// With KM_RUN_HIPGRAPH everything before the delivery is captured once and replayed.  A graph-only run (no k_pack)
+// zeroes the counters with a fill command of its own (launch_graph_fast).
 extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
   if (!b) return fail(KM_E_ARG, "null argument");
   const bool host_trace = knobs().host_trace;      // diagnostics: host time of the sections
@@ -972,9 +989,10 @@ extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
     if (b->in.n_items)
       launch_seed(b->in.n_items, st, wa, b->probes.count_fetches);
     if (b->tm.timed && f.timed_fine) HIPCHK(hipEventRecord(b->tm.ev[4], st));
-    // a batch's kernels run in ONE stream, in order (k_graph_pure after k_dfs): batches overlap with each
-    // other, every launch stream on a hardware queue of its own (see "streams" in host_common.h).  (Round 2 ran
-    // k_graph_pure beside k_dfs on a side stream per batch; KM_RUN_SERIAL selected today's order.)
+    // a batch's kernels run in ONE stream, in order: batches overlap with each other, every launch stream on a
+    // hardware queue of its own (see "streams" in host_common.h).  k_graph_pure needs nothing of k_dfs and runs
+    // beside it — rounds 2-3 on a side stream per batch, since round 6 as blocks of k_dfs's own launch;
+    // KM_RUN_SERIAL selects one launch each, k_graph_pure behind k_dfs.
     ga.use_need_full = 1;
     // diagnostics (KM_DFS_REPLAY=1|2): k_dfs twice, the SECOND launch is the one timed — its instruction
     // cache is warm; with 2 a 1 GiB memset in between flushes L2 / Infinity Cache (data cold again)
@@ -988,12 +1006,16 @@ extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
       }
       if (b->tm.timed) HIPCHK(hipEventRecord(b->tm.ev[4], st));
     }
-    launch_dfs(b, st, wa);
+    // (the walk-only run's k_graph_pure answers nothing, ga.dbg; the diagnostics measure k_dfs by itself)
+    const bool fused = knobs().fuse_pure && !f.serial && (f.stages & KM_STAGE_GRAPH) && ga.dbg == 0 && !dfs_replay &&
+                       wa.stamps == nullptr && wa.dbg == 0 && fuses_pure(b);
+    if (fused) launch_dfs_pure(b, st, wa, ga);
+    else launch_dfs(b, st, wa);
     HIPCHK(hipGetLastError());
     if (b->tm.timed) HIPCHK(hipEventRecord(b->tm.ev[1], st));
     b->big.bigdev_ran = b->big.big_entry && b->big.bigdev_armed;
     KMCHK(launch_big_walk_dev(b, st));
-    launch_pure(b, st, ga);
+    if (!fused) launch_pure(b, st, ga);
     launch_graph(b, st, ga);
     KMCHK(launch_big_graph_dev(b, st));
     HIPCHK(hipGetLastError());

@@ -145,10 +145,25 @@ __host__ __device__ inline uint64_t pure_lds_bytes(uint32_t hcap, uint32_t words
 // Unflagged targets (node list == the target's own k-mers, final right after k_seed):
 // decide whether the graph is the bare reference chain — all (k-1)-mer prefixes distinct
 // and the last k-mer's suffix not among them — and if so emit its single path.  Small LDS
-// (prefix keys only), so it runs at full occupancy and overlaps k_dfs on a second stream.
-// Everything else is left to k_graph through need_full[].
+// (prefix keys only).  Everything else is left to k_graph through need_full[].
+//
+// The pass needs nothing of k_dfs — tflag, status, n_ref, node_cnt and packed of an unflagged target and
+// n_flagged[0] are final when k_seed ends — and by default runs in k_dfs's own launch (k_dfs_pure below), its waves
+// filling the wave slots the short walks leave while the longest ones finish.  For that it must not look at anything
+// k_dfs writes while it runs: it tests tflag[t] FIRST and uses or writes nothing of a flagged target — not its status
+// (k_dfs stores T_NEEDS_BIG, the node limit, ... there; the word is loaded with the other header words and dropped
+// unread), not g_status / t_npaths / t_pathbase / t_nruns / t_refmax (the epilogue's).  Who writes those five for a flagged target, in every step (a reused workspace holds the last step's):
+//   epilogue on, answered by it (pools exhausted included): the epilogue, all five;
+//   epilogue on, every other exit of k_dfs (target does not fit the tier, walk ended with a status or unanswerable,
+//     block 0's hand-over of what is beyond the grid): t_refmax = NOT_BARE by k_dfs and an entry of `left`;
+//     k_graph takes the entry and writes the other four on every exit (status not OK included), block 0 of k_graph
+//     for the entries beyond ITS grid;
+//   epilogue off (KM_EPILOGUE=0, the graph-only rerun): the target is an entry of k_seed's flagged list, k_graph
+//     takes it and writes all five on every exit, block 0 for the entries beyond its grid.
+// need_full[t] of a flagged target is written by nobody and read by k_graph alone, which uses it only under !tflag.
+// The appends go to different counters (work_n[1] here, n_left in k_dfs), the path pools' to atomics.
 template <int K>
-__global__ __launch_bounds__(64) void k_graph_pure(GraphArgs a) {
+__device__ __forceinline__ void pure_body(GraphArgs a, const uint32_t t) {
   if constexpr (K != 0) {               // instantiated for one k: shifts and masks fold
     a.k = K;
     a.kmask = K >= 32 ? ~0ull : ((1ull << (2 * K)) - 1);
@@ -158,19 +173,19 @@ __global__ __launch_bounds__(64) void k_graph_pure(GraphArgs a) {
   // one wave per target: this pass runs beside k_dfs, it should take few wave slots
   const uint32_t lane = threadIdx.x & 63u, NT = 64;
   const uint32_t tid = lane;
-  const uint32_t t = blockIdx.x;
-  const uint32_t h_status = a.status[t], h_tflag = a.tflag[t];   // header words requested together
+  // header words requested together.  The status of a FLAGGED target is loaded with the others (a load behind the
+  // tflag test would put one more round trip into every unflagged target's chain) while k_dfs may be storing it:
+  // whatever value arrives is dropped by the return below, nothing is derived from it.
+  const uint32_t h_tflag = a.tflag[t], h_status = a.status[t];
   const uint32_t n_ref = a.n_ref[t];
   const uint64_t nb = a.node_base[t];
   const uint64_t h_woff = a.woff[t];
-  // (a flagged target's t_refmax belongs to k_dfs when its epilogue is on — every exit of its fast tier writes it —
-  // and to k_graph, which resets it before it decides anything)
-  if (tid == 0 && !(a.dfs_answers && h_tflag)) a.t_refmax[t] = NOT_BARE;
+  if (h_tflag) return;                         // k_dfs's and k_graph's: see above
+  if (tid == 0) a.t_refmax[t] = NOT_BARE;
   if (h_status != T_OK) {
     if (tid == 0) { a.need_full[t] = 0; a.g_status[t] = T_OK; a.t_npaths[t] = 0; a.t_pathbase[t] = 0; a.t_nruns[t] = 0; }
     return;
   }
-  if (h_tflag) return;                         // k_graph handles it once k_dfs is done
   const uint32_t hcap = a.hcap_pure;                        // slots of the position table: a power of two >= 4 (n_ref + 1)
   if ((uint64_t)4 * (n_ref + 2) > (uint64_t)hcap || n_ref >= 0xFFFFu || (a.dbg != 0 && !(a.dbg & 0x80u))) {
     if (tid == 0) { a.need_full[t] = 1; if (a.work_list) a.work_list[a.work_n[0] + atomicAdd(&a.work_n[1], 1u)] = t; }
@@ -267,6 +282,25 @@ __global__ __launch_bounds__(64) void k_graph_pure(GraphArgs a) {
   }
 }
 
+template <int K>
+__global__ __launch_bounds__(64) void k_graph_pure(GraphArgs a) {
+  pure_body<K>(a, blockIdx.x);
+}
+
+// k_dfs and k_graph_pure in one launch: blocks [0, n_dfs_blocks) are k_dfs's (dispatched first — the long walks
+// start at once), block n_dfs_blocks + t is k_graph_pure's for target t.  The two roles share no state (see above);
+// the launch's dynamic LDS is k_dfs's, and the host launches this kernel only where that is the larger of the two
+// (batch_host.h: fuses_pure).
+template <int K>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES_PER_EU)))
+void k_dfs_pure(WalkArgs wa, GraphArgs ga, uint32_t n_dfs_blocks) {
+  if (blockIdx.x >= n_dfs_blocks) {
+    pure_body<K>(ga, blockIdx.x - n_dfs_blocks);
+    return;
+  }
+  dfs_body<false, K>(wa, blockIdx.x, n_dfs_blocks);
+}
+
 // Direct mode (large tier, a.tids given): block b works on target tids[b].  LDS tier: block b
 // works on entry b of the work list (GraphArgs::work_list) — the blocks that have something to do
 // are the first ones of the grid and are dispatched together; the others leave after one load
@@ -293,9 +327,13 @@ __global__ __launch_bounds__(GRAPH_THREADS) void k_graph(GraphArgs a0) {
     if (blockIdx.x == 0 && n_total > gridDim.x) {
       for (uint32_t e = gridDim.x + threadIdx.x; e < n_total; e += GRAPH_THREADS) {
         const uint32_t tt = entry(e);
+        // (every entry gets its words written, as by a block of its own: a flagged target has no other writer)
+        a0.t_refmax[tt] = NOT_BARE; a0.t_npaths[tt] = 0; a0.t_pathbase[tt] = 0; a0.t_nruns[tt] = 0;
         if (a0.status[tt] == T_OK) {
-          a0.g_status[tt] = T_NEEDS_BIG; a0.t_npaths[tt] = 0; a0.t_pathbase[tt] = 0; a0.t_nruns[tt] = 0;
+          a0.g_status[tt] = T_NEEDS_BIG;
           if (a0.big_ctl) { const uint32_t at = atomicAdd(&a0.big_ctl[1], 1u); if (at < a0.big_slots) a0.big_graph[at] = tt; }
+        } else {
+          a0.g_status[tt] = T_OK;
         }
       }
     }
@@ -342,7 +380,11 @@ __global__ __launch_bounds__(GRAPH_THREADS) void k_graph(GraphArgs a0) {
   const uint64_t nb = a.node_base[t];
   const uint64_t h_woff = a.woff[t];
   if (h_status != T_OK) {
-    if (tid == 0) { a.g_status[t] = T_OK; a.t_npaths[t] = 0; a.t_pathbase[t] = 0; a.t_nruns[t] = 0; }
+    // (t_refmax as well: a flagged target that k_dfs left with a status has no other writer when the epilogue is off.
+    // No test can see this store: the delivery reads a target's path words and t_refmax only under status == OK &&
+    // g_status == OK (deliver_kernel.h: out_counts_of) and no call hands out the raw word.  It is here so that a
+    // reused workspace never holds the last step's word for such a target, whoever reads it one day.)
+    if (tid == 0) { a.g_status[t] = T_OK; a.t_npaths[t] = 0; a.t_pathbase[t] = 0; a.t_nruns[t] = 0; a.t_refmax[t] = NOT_BARE; }
     return;
   }
   if (a.use_need_full && !h_tflag && !h_need) return;   // answered by k_graph_pure

@@ -196,7 +196,9 @@ struct Staging {
 // shares a queue with ANOTHER batch's launch stream; 0.34 when launch streams themselves end up pairwise
 // on one queue; 0.21 with 8 queues and the side streams on queues of their own; 0.19 with 8 queues and no
 // side stream at all: a batch's kernels in ONE stream, every launch stream on a queue of its own.  So
-// (1) there is no side stream any more, (2) the library asks for 8 hardware queues unless the environment
+// (1) there is no side stream any more — the overlap of k_graph_pure with k_dfs it was there for comes from ONE
+// launch that holds the blocks of both (graph_kernel.h: k_dfs_pure), which needs no stream or queue of its
+// own —, (2) the library asks for 8 hardware queues unless the environment
 // says otherwise — when it is loaded, i.e. before the HIP runtime reads its settings — and (3) launch
 // streams come from a per-device pool created once.
 namespace {

@@ -592,8 +592,11 @@ __global__ __launch_bounds__(SEED_BLOCK) void k_seed(WalkArgs a) {
 #ifndef KM_DFS_WAVES_PER_EU
 #define KM_DFS_WAVES_PER_EU 4
 #endif
+// The body of k_dfs as a device function: block `bid` of `n_blocks` (k_dfs: its own blockIdx.x of gridDim.x; the fused
+// kernel k_dfs_pure of graph_kernel.h: its first n_blocks blocks).  Everything that was indexed by the block —
+// the entry of the flagged list, flag_rec, f_ws, g_ws, stamps — is indexed by `bid`.
 template <bool BIG, int K>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES_PER_EU))) void k_dfs(WalkArgs a) {
+__device__ __forceinline__ void dfs_body(const WalkArgs a, const uint32_t bid, const uint32_t n_blocks) {
   extern __shared__ __align__(16) unsigned char smem[];
   const uint32_t lane = (uint32_t)lane_id();
   // diagnostics (KM_SEED_STAMPS in the environment): when this wave started and ended, 100 MHz clock
@@ -616,16 +619,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
 #endif
   const TableView tab = specialized_view<K>(a.tab);
   const int k = tab.k;
-  // the target: fast tier — entry blockIdx.x of k_seed's list of flagged targets, with what the
+  // the target: fast tier — entry bid of k_seed's list of flagged targets, with what the
   // walk needs of it in one record (requested together with the length of the list); large tier —
   // a list of target ids from the host
   uint32_t t, n_ref, node_cap;
   uint64_t nb, wo, fwo;
   if constexpr (BIG) {
     const uint32_t n_list = a.n_list_dev ? *a.n_list_dev : a.n_list_host;
-    if (blockIdx.x >= n_list) return;
-    if (a.big_prep && blockIdx.x >= a.big_slots) return;
-    t = a.list[blockIdx.x];
+    if (bid >= n_list) return;
+    if (a.big_prep && bid >= a.big_slots) return;
+    t = a.list[bid];
     if (a.status[t] != T_OK && a.status[t] != T_NEEDS_BIG) return;
     n_ref = a.n_ref[t];
     nb = a.node_base[t];
@@ -636,10 +639,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
       if (at < a.loop_cap) { a.loop_list[2 * at] = t; a.loop_list[2 * at + 1] = 0xFFFFFFFFu; }
     }
     if (a.big_prep) {
-      // the device's own large tier: slot blockIdx.x of the region; the seed kernel's counts move there
+      // the device's own large tier: slot bid of the region; the seed kernel's counts move there
       const uint64_t need = (uint64_t)max(n_ref, a.max_node + a.max_stack) + 1;
       if (need > (uint64_t)a.big_entry || a.status[t] != T_NEEDS_BIG) return;          // (left to the host)
-      const uint64_t nb_new = a.big_region + (uint64_t)blockIdx.x * a.big_entry;
+      const uint64_t nb_new = a.big_region + (uint64_t)bid * a.big_entry;
       for (uint32_t j = lane; j < n_ref; j += 64) a.node_cnt[nb_new + j] = a.node_cnt[nb + j];
       if (lane == 0) { a.node_base[t] = nb_new; a.node_cap[t] = a.big_entry; }
       nb = nb_new;
@@ -649,20 +652,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
     wo = a.woff[t];
     fwo = a.fw_off[t];
   } else {
-    const uint4 r0 = a.flag_rec[2 * blockIdx.x], r1 = a.flag_rec[2 * blockIdx.x + 1];
+    const uint4 r0 = a.flag_rec[2 * bid], r1 = a.flag_rec[2 * bid + 1];
     const uint32_t n_list = *a.n_list_dev;
     // The grid follows the number of flagged targets the batch's last delivery reported (kmgpu.hip: launch_dfs), not
     // the batch size.  Should more be flagged than there are blocks, block 0 hands the rest to the large tier, as
     // any target is that this tier cannot hold (the next run's grid is larger).
-    if (blockIdx.x == 0 && n_list > gridDim.x) {
-      for (uint32_t e = gridDim.x + lane; e < n_list; e += 64) {
+    if (bid == 0 && n_list > n_blocks) {
+      for (uint32_t e = n_blocks + lane; e < n_list; e += 64) {
         const uint32_t te = a.flag_rec[2 * e].x;
         a.status[te] = T_NEEDS_BIG;
         if (a.epi != nullptr) { a.epi->t_refmax[te] = NOT_BARE; a.epi->left[atomicAdd(a.epi->n_left, 1u)] = te; }
         if (a.big_ctl) { const uint32_t at = atomicAdd(&a.big_ctl[0], 1u); if (at < a.big_slots) a.big_walk[at] = te; }
       }
     }
-    if (blockIdx.x >= n_list) return;
+    if (bid >= n_list) return;
     t = r0.x; n_ref = r0.y; nb = ((uint64_t)r0.w << 32) | r0.z;
     fwo = r1.x; wo = r1.y;
     node_cap = n_ref + a.fast_extra;
@@ -671,11 +674,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
   unsigned char* wsb;
   unsigned char* fwb;
   if constexpr (BIG) {
-    wsb = a.g_ws + (uint64_t)blockIdx.x * a.g_stride;
+    wsb = a.g_ws + (uint64_t)bid * a.g_stride;
     fwb = wsb + walk_lds_bytes(a.hs_cap, a.words_cap, a.bcap, a.pcap, 4);
   } else {
     wsb = smem;
-    fwb = a.f_ws + (uint64_t)blockIdx.x * a.f_stride;
+    fwb = a.f_ws + (uint64_t)bid * a.f_stride;
   }
   // k = 32: the k-mer T^32 is the value EMPTY itself (no 64-bit value is free to mark an empty slot), so the hashed
   // set cannot hold it.  It gets a slot of its own instead — ALL_T, the first of 64 slots kept out of the hashed
@@ -1710,7 +1713,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
   }
 
   if (a.stamps && lane == 0) {
-    unsigned long long* o = a.stamps + 32ull * blockIdx.x;
+    unsigned long long* o = a.stamps + 32ull * bid;
     o[0] = life0; o[1] = __builtin_amdgcn_s_memrealtime(); o[2] = t; o[3] = n_nodes - n_ref; o[4] = life1; o[5] = life2; o[6] = 0; o[7] = lifeB; o[8] = lifeC;
 #ifdef KM_DFS_COUNTERS
     o[19] = dt_spec; o[20] = dt_book; o[21] = dt_gen; o[22] = dt_bload; o[23] = dt_rejoin; o[24] = dt_unwind; o[25] = dt_align;
@@ -1732,6 +1735,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES
       a.fetches[t] += fetch_u;
     }
   }
+}
+
+template <bool BIG, int K>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES_PER_EU))) void k_dfs(WalkArgs a) {
+  dfs_body<BIG, K>(a, blockIdx.x, gridDim.x);
 }
 
 }  // namespace kmd

@@ -917,6 +917,8 @@ class Batch:
         check(self._lib.km_batch_sync(self._b))
 
     def timings(self):
+        """km_batch_timings: (walk, graph, walk + graph, k_seed, k_pack, k_dfs, delivery kernels, copy) in ms.  Without
+        KM_RUN_SERIAL k_dfs and k_graph_pure are one launch: walk and k_dfs contain the pure-chain pass, graph does not."""
         ms = (C.c_float * 8)()
         check(self._lib.km_batch_timings(self._b, ms))
         return tuple(float(x) for x in ms)

@@ -38,7 +38,8 @@ for r in rows("*memory_copy_trace.csv"):
                    col(r, "Stream_Id", "Queue_Id") or "?"))
 kern.sort()
 copies.sort()
-ours = ("k_pack", "k_seed", "k_dfs", "k_graph_pure", "k_graph", "k_out_scan", "k_out_pack")
+# (k_dfs_pure: k_dfs and k_graph_pure as one launch, the default since round 6 — a step then has six kernels, not seven)
+ours = ("k_pack", "k_seed", "k_dfs", "k_dfs_pure", "k_graph_pure", "k_graph", "k_out_scan", "k_out_pack")
 steps_by_stream = collections.defaultdict(list)        # stream -> list of dicts
 cur = {}
 for s, e, name, st in kern:
@@ -49,7 +50,7 @@ for s, e, name, st in kern:
         steps_by_stream[st].append(cur[st])
     step = cur.get(st)
     if step is None:
-        # k_graph_pure runs on the batch's side stream: attach it to the step in flight that started last
+        # (round 2: k_graph_pure ran on the batch's side stream) attach it to the step in flight that started last
         live = [v for v in cur.values() if v["start"] <= s]
         step = max(live, key=lambda v: v["start"]) if live else None
         if step is None:

@@ -627,6 +627,44 @@ int kmjf_query_text(kmjf_t* h, const uint64_t* kmers, uint64_t n, int out_fd, km
 /* the time of the sizes / scan / write kernels of the calling thread's last call of the four above, by HIP events */
 int km_dump_kernel_ms(float* ms);
 
+/* ---- scan: the k-mers of sequences, cut and looked up on the device ------------------------- */
+/* Sequences go to the device as text; their k-mers are cut there and looked up in the uploaded table.  The rule:
+ *   A sequence is a run of bytes.  ACGTacgt are bases; every other byte is a non-base.
+ *   A window is k consecutive bytes of ONE sequence.  Windows never span two sequences; a sequence shorter than k
+ *   has none.
+ *   A window is valid iff all k bytes are bases.  A window with a non-base is skipped.
+ *   The count of a valid window is what kmjf_query_batch returns for its packed k-mer (A 0, C 1, G 2, T 3, the first
+ *   base in the most significant used bits): that of the canonical form for a canonical table, 0 for an absent k-mer.
+ *   The k-mer printed is what `query` prints: min(k-mer, reverse complement) for a canonical table, the k-mer as
+ *   given otherwise.
+ * text holds the sequences end to end with nothing between them: sequence q is text[seq_off[q] .. seq_off[q + 1]).
+ * seq_off has n_seqs + 1 entries and ascends; equal neighbours are an empty sequence.  No byte value is reserved.
+ * A call takes at most KM_SCAN_MAX_SEQS sequences (KM_E_ARG beyond); the text has no limit of its own: it crosses
+ * in pieces of KM_COUNT_STAGE_BYTES, and a sequence may span any number of them.
+ * Both calls: KM_E_ARG for null pointers and for offsets that do not ascend, KM_E_STATE without an uploaded table;
+ * with n_seqs == 0 or no bytes at all they return KM_OK and touch neither out nor the descriptor.
+ * stream: a hipStream_t, NULL = one of the library's own.  Nothing of a call is left running on the device. */
+#define KM_SCAN_MAX_SEQS (1ull << 26)
+typedef struct {
+  uint64_t total;      /* sum of the counts of the valid windows                      */
+  uint64_t n_kmers;    /* valid windows                                               */
+  uint64_t n_zero;     /* valid windows with count 0                                  */
+  uint64_t n_skipped;  /* windows of this sequence with a non-base                    */
+  uint64_t n_nonbase;  /* bytes of this sequence that are not ACGTacgt                */
+  uint32_t min, max;   /* over the valid windows; 0xFFFFFFFF and 0 when n_kmers == 0  */
+} km_cov_t;
+/* out[n_seqs]: the statistics of every sequence (an empty one: zeros, min 0xFFFFFFFF).  All fields are integer sums,
+ * minima and maxima: the result does not depend on how the work was spread. */
+int kmjf_cov_seqs(kmjf_t* h, const uint8_t* text, const uint64_t* seq_off, uint64_t n_seqs, km_cov_t* out, void* stream);
+/* One KM_DUMP_COLUMN line ("MER COUNT\n") per valid window to the descriptor out_fd, sequence after sequence, windows
+ * in text order; a skipped window has no line.  stats (may be NULL): records_in = the windows of all sequences,
+ * records_out = the lines written.  The descriptor is treated as kmjf_query_text treats it: KM_E_IO when it is not
+ * open or a write fails, and the library goes on. */
+int kmjf_scan_text(kmjf_t* h, const uint8_t* text, const uint64_t* seq_off, uint64_t n_seqs, int out_fd,
+                   km_dump_stats_t* stats, void* stream);
+/* the time of the scan kernels (extraction + lookup) of the calling thread's last call of the two above, by HIP events */
+int km_scan_kernel_ms(float* ms);
+
 /* ---- measurement helpers (bench.py at N = 1 holds no device buffers of its own) ------------- */
 int km_device_sync(int device);                                    /* hipDeviceSynchronize on `device`          */
 /* device-to-device copy of `bytes` bytes, `reps` times: read + write GB/s (the box's large-copy

@@ -1,5 +1,5 @@
 """``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, ``count``, ``merge``, ``histo``,
-``stats``, ``dump`` and ``query``.
+``stats``, ``dump``, ``query`` and ``cov``.
 
 Same flags, same ``#key:value`` echo, same TSV and ``#Elapsed time`` trailer as
 km/tools/find_mutation.py:17-60 and km/argparser/find_mutation.py:4-58, so the
@@ -290,6 +290,47 @@ def main_min_cov(args, out=None):
         out.write("%s\t%d\t%d\t%d\t%d\t%.2f\t%d\t%d\n" % ((db,) + tuple(res)))
 
 
+COV_HEADER = "DB\ttarget\trecord\tcount\tlength\tmin\tmax\tmean\tkmer_nb\tkmer_nb_0\tkmer_nb_skipped\n"
+
+
+def cov_row(db, target, record, length, c):
+    """One line of `cov`: the numbers of min_cov in its formats and the skipped windows behind them; a record without
+    a valid window has NA for min, max and mean."""
+    n, total = int(c["n_kmers"]), int(c["total"])
+    head = "%s\t%s\t%d\t%d\t%d\t" % (db, target, record, total, length)
+    mid = "%d\t%d\t%.2f" % (int(c["min"]), int(c["max"]), float(total) / n) if n else "NA\tNA\tNA"
+    return head + mid + "\t%d\t%d\t%d\n" % (n, int(c["n_zero"]), int(c["n_skipped"]))
+
+
+def main_cov(args, out=None):
+    """`cov [-o out.tsv] -t <targets.fa ...|dir> <db.jf> [<db.jf> ...]`: the coverage of EVERY record of the target
+    files in every database, one row per database and record, database-major.  Where `min_cov` joins the records of
+    one file into one sequence and stops at a non-ACGT letter, here a record is a sequence of its own and a window
+    with such a letter is skipped and counted.  All records of all files go to the device in one call per database
+    (common.cov_many); one database is in HBM at a time."""
+    from . import common
+    from . import count as kc
+    files = list_target_files(args.targets)
+    names, seqs = [], []
+    for path in files:                   # everything is read before anything touches the GPU
+        stem = os.path.splitext(os.path.basename(path))[0]
+        for i, seq in enumerate(kc._fasta_records(path), 1):
+            names.append((stem, i))
+            seqs.append(seq)
+    fh = open(args.output, "w") if args.output else None
+    out = fh if fh is not None else (sys.stdout if out is None else out)
+    try:
+        out.write(COV_HEADER)
+        for db in args.jellyfish_fn:
+            cov = common.cov_many(db, seqs)
+            common.close(db)
+            for (stem, i), seq, c in zip(names, seqs, cov):
+                out.write(cov_row(db, stem, i, len(seq), c))
+    finally:
+        if fh is not None:
+            fh.close()
+
+
 def main_count(args, err=None):
     """`jellyfish count -m K [-C] -L N -s SIZE -o OUT reads..` on the GPU (km_amd.count): the k-mers of the read
     files counted on the device, the records with count >= -L written to OUT (read by every tool here).  The file
@@ -528,7 +569,26 @@ def build_parser():
     qr.add_argument("-o", "--output", default=None, help="output file (default: standard output)")
     qr.add_argument("db", metavar="db.jf", help="a binary/sorted file")
     qr.add_argument("mers", nargs="*", metavar="MER", help="k-mers of the file's k, letters of ACGT")
+    cv = sub.add_parser("cov", help="coverage of every record of the target files in every database, k-mers cut on the GPU")
+    cv.add_argument("-t", "--targets", nargs="+", required=True,
+                    help="target FASTA files or one directory; when the databases follow directly, the targets end at "
+                         "the first argument that is neither a directory nor a file that starts like FASTA")
+    cv.add_argument("-o", "--output", default=None, help="output file (default: standard output)")
+    cv.add_argument("jellyfish_fn", nargs="*", metavar="db.jf", help="one or more databases")
     return parser
+
+
+def _looks_like_target(path):
+    """A directory, or a file whose first byte is '>' (FASTA) or the gzip magic: what `cov -t` takes as a target when
+    the databases follow it without another option in between.  Anything else, a missing file too, is a database."""
+    if os.path.isdir(path):
+        return True
+    try:
+        with open(path, "rb") as fh:
+            head = fh.read(2)
+    except OSError:
+        return False
+    return head[:1] == b">" or head == b"\x1f\x8b"
 
 
 def parse_args(argv=None, parser=None):
@@ -543,6 +603,13 @@ def parse_args(argv=None, parser=None):
         parser.error("merge: --max, --min and --subtract exclude each other")
     if args._cmd == "query" and not args.sequence and not args.mers:
         parser.error("query: nothing to query: give -s FILE or MER arguments")
+    if args._cmd == "cov" and not args.jellyfish_fn:     # `-t a.fa b.fa db.jf ..`: -t took the databases too
+        n = 0
+        while n < len(args.targets) and _looks_like_target(args.targets[n]):
+            n += 1
+        args.targets, args.jellyfish_fn = args.targets[:n], args.targets[n:]
+        if not args.targets or not args.jellyfish_fn:
+            parser.error("cov: give -t <targets.fa ...|dir> and at least one db.jf")
     return args
 
 
@@ -577,6 +644,8 @@ def main(argv=None):
         main_dump(args)
     elif cmd == "query":
         main_query(args)
+    elif cmd == "cov":
+        main_cov(args)
     else:
         parser.print_help(sys.stderr)
         sys.exit(1)

@@ -10,8 +10,8 @@ framing the readers of this project load, sorted by key; ``write_jellyfish`` wri
 record order (sorted on the GPU), as ``Counter.write_jf`` does for records still on the device.
 ``histo_file``, ``format_histo`` and ``format_stats`` are behind ``python -m km_amd histo`` / ``stats``: the histogram
 of a file's counts and its four statistics in one pass on the GPU.  ``dump_file`` and ``query_file`` are behind
-``dump`` / ``query``: a file's records, or the counts of given k-mers, as text built on the GPU.  Only the standard
-library and numpy.
+``dump`` / ``query``: a file's records, or the counts of given k-mers, as text built on the GPU; the k-mers of
+``query -s`` files are cut there too.  Only the standard library and numpy.
 """
 
 import contextlib
@@ -270,17 +270,22 @@ def query_keys(k, canonical, mers=(), seq_files=()):
 def query_file(db_path, mers=(), seq_files=(), out=None, device=0):
     """What `jellyfish query db.jf [-s FILE]... [MER ...]` prints: "MER COUNT" per k-mer, 0 for one that is not in
     the table; the windows of the -s files first, in the order given, then the MER arguments.  For a canonical database
-    the canonical k-mer is looked up and printed.  Lookups and text are made on the GPU (Database.query_text); the
-    k-mers of the -s files are extracted on the host with numpy -> the dict of km_dump_stats_t.  This project's reading
-    of the command, not checked against a run of Jellyfish."""
+    the canonical k-mer is looked up and printed.  The records of the -s files go to the device as text, where their
+    k-mers are cut, looked up and printed (Database.scan_text, one call per file); the MER arguments are packed here
+    and go through Database.query_text -> the dict of km_dump_stats_t, summed over those calls.  This project's
+    reading of the command, not checked against a run of Jellyfish."""
     info = _lib.jf_file_info(db_path)
     check_mers(mers, info["k"])                           # before the table is loaded
-    keys = query_keys(info["k"], info["canonical"], mers=mers, seq_files=seq_files)
+    keys = query_keys(info["k"], info["canonical"], mers=mers)
+    files = [list(_fasta_records(path)) for path in seq_files]     # (a missing file fails before `out` is opened)
     db = _lib.Database.open(db_path)
     try:
         db.upload(device)
         with _text_out(out) as fd:
-            return db.query_text(keys, fd)
+            stats = [db.scan_text(records, fd) for records in files]       # files first, then the mers
+            if keys.size:
+                stats.append(db.query_text(keys, fd))
+        return {name: sum(st[name] for st in stats) for name in ("records_in", "records_out", "bytes_out", "pieces")}
     finally:
         db.close()
 

@@ -16,7 +16,8 @@
 // writes a byte outside [tile_off[tile], tile_off[tile] + the tile's bytes).
 //
 // Where the records come from is a small decode functor: DumpRaw reads them as they sit in a file, DumpArrays from
-// (keys, counts) arrays on the device (a finished counter; the answer of k_query).
+// (keys, counts) arrays on the device (a finished counter; the answer of k_query), DumpScan (scan_kernel.h) from the
+// window starts of scanned sequences.  A source says per record whether it has a line at all: line(i).
 #pragma once
 #include "dump_text.h"
 #include "table_kernels.h"
@@ -40,6 +41,7 @@ struct DumpRule {
 struct DumpRaw {
   const uint8_t* raw;
   uint32_t kb, cb;
+  __device__ bool line(uint32_t) const { return true; }
   __device__ uint32_t count(uint32_t i) const {
     if (kb == 8 && cb == 4) return reinterpret_cast<const uint32_t*>(raw)[3ull * i + 2];
     const uint8_t* p = raw + (uint64_t)i * (kb + cb) + kb;
@@ -62,14 +64,15 @@ struct DumpRaw {
 struct DumpArrays {
   const uint64_t* keys;
   const uint32_t* counts;
+  __device__ bool line(uint32_t) const { return true; }
   __device__ uint32_t count(uint32_t i) const { return counts[i]; }
   __device__ uint64_t key(uint32_t i) const { return keys[i]; }
 };
 
-// the line length of record i of the piece (0: none, or filtered out) and its count
+// the line length of record i of the piece (0: none, no line, or filtered out) and its count
 template <typename Src>
 __device__ inline uint32_t dump_lane_len(const Src& src, uint32_t i, uint32_t n, const DumpRule& r, uint32_t* count) {
-  if (i >= n) return 0;
+  if (i >= n || !src.line(i)) return 0;
   const uint32_t c = src.count(i);
   *count = c;
   return kmdump::kept(c, r.lower, r.upper) ? kmdump::line_len(r.k, kmdump::digits(c), r.fmt) : 0u;

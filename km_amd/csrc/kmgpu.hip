@@ -21,6 +21,8 @@
 //                  or a file in one streaming pass (a file: RecordFile, a Staging of the call's own, CallStream)
 //   dump_host.h    km_dump_text, km_jf_dump, km_counter_dump, kmjf_query_text: records as the text of `dump` / `query`,
 //                  formatted on the device piece by piece and written to a descriptor (a Staging in, a Staging out)
+//   scan_host.h    kmjf_cov_seqs, kmjf_scan_text: the k-mers of sequences cut and looked up on the device, as per-sequence
+//                  coverage statistics or as the text of `query` (a Staging in; the text through dump_host.h's DumpPipe)
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
 #include <hip/hip_runtime.h>
@@ -61,7 +63,9 @@
 #include "merge_pieces.h"
 #include "table_kernels.h"
 #include "walk_kernel.h"
-#include "setops_kernel.h"      // (last: the kernels before it keep their places in the code object)
+#include "setops_kernel.h"      // (after those above: the kernels before it keep their places in the code object)
+#include "scan_kernel.h"
+#include "scan_rule.h"
 
 using namespace kmd;
 
@@ -77,3 +81,4 @@ using namespace kmd;
 #include "setops_host.h"
 #include "histo_host.h"
 #include "dump_host.h"
+#include "scan_host.h"

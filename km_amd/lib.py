@@ -44,6 +44,7 @@ SYMBOLS = [
     "km_counter_set_records", "km_counter_set_jf", "km_counter_finish_range",
     "km_histo_layout", "km_counter_histo", "km_jf_histo", "km_histo_kernel_ms", "km_histo_text", "km_histo_stats_text",
     "km_dump_text", "km_jf_dump", "km_counter_dump", "kmjf_query_text", "km_dump_kernel_ms",
+    "kmjf_cov_seqs", "kmjf_scan_text", "km_scan_kernel_ms",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
 ]
 
@@ -96,6 +97,11 @@ class TextState(C.Structure):
     _fields_ = [("format", C.c_int32), ("line", C.c_int32), ("open", C.c_int32), ("reserved", C.c_int32),
                 ("offset", C.c_uint64)]
 
+
+# km_cov_t (include/kmgpu.h): the coverage statistics of one sequence
+COV_DTYPE = np.dtype([("total", "<u8"), ("n_kmers", "<u8"), ("n_zero", "<u8"), ("n_skipped", "<u8"),
+                      ("n_nonbase", "<u8"), ("min", "<u4"), ("max", "<u4")])
+assert COV_DTYPE.itemsize == 48
 
 _P16 = C.POINTER(C.c_uint16)
 _P32 = C.POINTER(C.c_uint32)
@@ -274,6 +280,9 @@ def load():
         "km_counter_dump": [vp, i32, i32, u32, u32, C.POINTER(DumpStats)],
         "kmjf_query_text": [vp, vp, u64, i32, C.POINTER(DumpStats), vp],
         "km_dump_kernel_ms": [C.POINTER(C.c_float)],
+        "kmjf_cov_seqs": [vp, vp, vp, u64, vp, vp],
+        "kmjf_scan_text": [vp, vp, vp, u64, i32, C.POINTER(DumpStats), vp],
+        "km_scan_kernel_ms": [C.POINTER(C.c_float)],
         "km_device_count": [C.POINTER(i32)],
         "km_device_sync": [i32],
         "km_device_copy_GBs": [i32, u64, i32, C.POINTER(dbl)],
@@ -477,6 +486,28 @@ class Database:
         st = DumpStats()
         check(self._lib.kmjf_query_text(self._h, ptr(kmers) if kmers.size else None, kmers.size, out_descriptor(out_fd),
                                         C.byref(st), C.c_void_p(stream or 0)))
+        return _dump_stats_dict(st)
+
+    def cov_seqs(self, seqs, stream=None):
+        """kmjf_cov_seqs: the coverage statistics of every sequence of `seqs` (str, bytes or uint8 arrays) over its
+        windows of k bases, cut and looked up on the device -> a structured array of km_cov_t (COV_DTYPE), one cell
+        per sequence.  A window with a byte outside ACGTacgt is skipped and counted in n_skipped; a sequence
+        without a valid window has n_kmers 0, min 0xFFFFFFFF and max 0."""
+        text, off = pack_sequences(seqs)
+        out = np.zeros(off.size - 1, COV_DTYPE)
+        out["min"] = 0xFFFFFFFF                             # (a call without bytes touches nothing)
+        check(self._lib.kmjf_cov_seqs(self._h, ptr(text) if text.size else None, ptr(off), off.size - 1,
+                                      ptr(out) if out.size else None, C.c_void_p(stream or 0)))
+        return out
+
+    def scan_text(self, seqs, out_fd, stream=None):
+        """kmjf_scan_text: one "MER COUNT" line per valid window of every sequence of `seqs`, in order, to the
+        descriptor out_fd: what `query -s` prints; the k-mers are cut, looked up and printed on the device -> the
+        dict of km_dump_stats_t (records_in: all windows, records_out: the lines)."""
+        text, off = pack_sequences(seqs)
+        st = DumpStats()
+        check(self._lib.kmjf_scan_text(self._h, ptr(text) if text.size else None, ptr(off), off.size - 1,
+                                       out_descriptor(out_fd), C.byref(st), C.c_void_p(stream or 0)))
         return _dump_stats_dict(st)
 
 
@@ -788,6 +819,14 @@ def dump_kernel_ms():
     Database.query_text."""
     ms = C.c_float()
     check(load().km_dump_kernel_ms(C.byref(ms)))
+    return float(ms.value)
+
+
+def scan_kernel_ms():
+    """km_scan_kernel_ms: the time of the scan kernels (extraction + lookup) of this thread's last Database.cov_seqs /
+    Database.scan_text."""
+    ms = C.c_float()
+    check(load().km_scan_kernel_ms(C.byref(ms)))
     return float(ms.value)
 
 

@@ -272,7 +272,31 @@ int km_batch_result(km_batch_t* b, km_batch_out_t* view, km_batch_sizes_t* sizes
 /* `steps` runs over `n` batches in flight, round robin (batch i % n on streams[i % n]): before a
  * batch is run again its previous delivery is awaited, at the end every batch's.  The loop of a
  * pipelined consumer (km/tools/find_mutation.py:47-58 over successive batches) without an
- * interpreter between the launches. */
+ * interpreter between the launches.
+ * Consecutive steps are PAIRED where they can be: k_seed of the next batch runs as blocks of the previous batch's
+ * k_dfs_pure launch (one kernel, k_dfs_pure_seed), so that the memory-bound k_seed fills what the latency-bound walk
+ * leaves idle.  Paired steps do NOT run on streams[]: the pump takes two streams of the library's pool for the call.
+ * One, the chain, gets k_pack and the paired launch of every step, in order; the other, the tail, waits for an event
+ * behind each paired launch and gets the rest of the walked batch's step (large tier, k_graph, delivery kernels, the
+ * copy) — so those copies follow each other on one stream.  The chain first waits for whatever the caller has put on
+ * a batch's own stream; when the call returns (also with an error) no batch refers to the two streams any more.
+ * A step CAN be paired when n >= 2, both batches have targets and the next one a walkable k-mer, both databases have
+ * k = 31 or neither, the previous batch's k_dfs and k_graph_pure share a launch, its walk blocks (as many as its last
+ * delivery reported flagged targets, + 25 %) are all resident on the device at once, and `stages` is plain walk +
+ * graph + delivery (no KM_RUN_SERIAL, KM_RUN_HIPGRAPH, KM_RUN_TIMED*, KM_RUN_COUNT_FETCHES); every other step is
+ * km_batch_run's own sequence on streams[i % n].  Results are the same either way.
+ * One chain gives up the overlap of n streams, so by default such a step IS paired only where that pays: n <= 4
+ * (more batches in flight is how a consumer hides the latency of small steps, and that needs their chains side by
+ * side: paired, 8 batches of 1 250-5 000 targets ran 1.4-2.1 x slower), a lean delivery (KM_DELIVER_LEAN: a full
+ * one is bound by its copies, which the tail would put one behind the other), and at least two seed blocks of the
+ * next batch (one per 256 k-mers of a target, rounded up per target) for each of the device's 16 wave slots per
+ * compute unit — 8 192 on 256 compute units, about 4 100 targets of 500 nt; below that the seeds are bound by latency
+ * like the walk beside them and nothing is won.
+ * KM_PUMP_UNPAIRED in `stages` (km_batch_run ignores both flags) or KM_PAIR_SEED=0 in the environment: no step is
+ * paired.  KM_PUMP_PAIRED or KM_PAIR_SEED=2: every step that can be paired is, whether it pays or not (tests,
+ * measurements); KM_PUMP_UNPAIRED wins over it. */
+#define KM_PUMP_UNPAIRED 1024
+#define KM_PUMP_PAIRED 2048
 int km_batch_pump(km_batch_t* const* batches, void* const* streams, int n, int steps, int stages);
 /* What the reference logs with -v from inside the walk and the graph, for the last run of `b` (any output may be
  * NULL): removed_ref_edges[n_targets] / nonref_edges[n_targets] — "Removed %d ref edges." (km/utils/Graph.py:198)
@@ -338,7 +362,8 @@ void km_report_free(char* text, uint64_t* row_off, int32_t* err);
  * dst == NULL only reports the size.  Stamped runs are slower; never use them for timing. */
 int km_batch_debug_stamps(km_batch_t* b, uint64_t* dst, uint64_t cap_words, uint64_t* n_words);
 /* Diagnostics: device counters of the last run — out4[0] flagged targets (k_seed), [1] unflagged targets
- * the pure-chain pass handed to k_graph, [2] flagged targets the epilogue of k_dfs left to k_graph, [3] 0. */
+ * the pure-chain pass handed to k_graph, [2] flagged targets the epilogue of k_dfs left to k_graph, [3] a host counter: how
+ * often, since the batch was made, its k_seed has run in another batch's walk launch (km_batch_pump's paired steps). */
 int km_batch_debug_counts(km_batch_t* b, uint32_t* out4);
 
 /* ---- linear_kmin -------------------------------------------------------------------------------

@@ -19,6 +19,8 @@ struct Knobs {
   bool speculate = true;        // KM_SPECULATE=0: k_dfs walks every chain one lookup after the other (results unchanged)
   bool dfs_grid_full = false;   // KM_DFS_GRID_FULL=1: one block of k_dfs per target of the batch, as before round 4
   bool fuse_pure = true;        // KM_FUSE_PURE=0: k_dfs and k_graph_pure as two launches, as before round 6 (results unchanged)
+  int pair_seed = 1;            // KM_PAIR_SEED=0: km_batch_pump never runs a batch's k_seed in another batch's walk launch; 2: wherever it can, also where it does not pay (results unchanged)
+  bool seed_waves = false;      // KM_SEED_WAVES=1: k_seed as single-wave blocks (k_seed_waves: what seed_body costs alone; results unchanged)
 };
 Knobs read_knobs() {
   Knobs q;
@@ -37,6 +39,8 @@ Knobs read_knobs() {
   q.speculate = num("KM_SPECULATE", 1) != 0;
   q.dfs_grid_full = num("KM_DFS_GRID_FULL", 0) != 0;
   q.fuse_pure = num("KM_FUSE_PURE", 1) != 0;
+  q.pair_seed = (int)num("KM_PAIR_SEED", 1);
+  q.seed_waves = num("KM_SEED_WAVES", 0) != 0;
   return q;
 }
 const Knobs& knobs() {
@@ -290,6 +294,12 @@ struct Timing {
   bool timed_deliver = false;
 };
 
+struct Pairing {                   // the paired pump (result_host.h): this batch's step ran on the pump's two streams
+  Event ev_walked;                   // recorded behind its walk launch on the chain; the tail waits for it (made on first use)
+  bool borrowed = false;             // last_stream is one of the pump's streams (until the pump returns)
+  uint32_t n_seeded = 0;             // diagnostics (km_batch_debug_counts): paired launches that seeded this batch so far
+};
+
 struct CapturedStep {              // KM_RUN_HIPGRAPH: km_batch_run captures, km_batch::drop_graph() forgets
   Graph graph;
   GraphExec gexec;
@@ -326,6 +336,7 @@ struct km_batch {
   PathPools paths;
   Timing tm;
   LaunchHints hints;
+  Pairing pair;
   CapturedStep cap;                    // the last member: it goes before the buffers it uses
 
   void drop_graph() { cap.gexec.reset(); cap.graph.reset(); }
@@ -718,6 +729,11 @@ static int launch_graph_fast(km_batch* b, hipStream_t st) {
 
 static void launch_seed(uint32_t n_items, hipStream_t st, const WalkArgs& wa, bool count_fetches) {
   if (wa.stamps) hipLaunchKernelGGL((k_seed<true, 0, true>), dim3(n_items), dim3(SEED_BLOCK), 0, st, wa);   // KM_SEED_STAMPS diagnostics
+  else if (knobs().seed_waves && !count_fetches && n_items < (1u << 29)) {
+    const dim3 g((4 / SEED_WAVE_RUNS) * n_items), blk(64);
+    if (wa.tab.k == 31) hipLaunchKernelGGL((k_seed_waves<31>), g, blk, SEED_WAVE_LDS, st, wa);
+    else hipLaunchKernelGGL((k_seed_waves<0>), g, blk, SEED_WAVE_LDS, st, wa);
+  }
   else if (wa.tab.k == 31) {
     if (count_fetches) hipLaunchKernelGGL((k_seed<false, 31, true>), dim3(n_items), dim3(SEED_BLOCK), 0, st, wa);
     else hipLaunchKernelGGL((k_seed<false, 31, false>), dim3(n_items), dim3(SEED_BLOCK), 0, st, wa);
@@ -919,6 +935,136 @@ struct RunFlags {
         count_fetches(s & KM_RUN_COUNT_FETCHES), timed(s & KM_RUN_TIMED), timed_fine(timed && !(s & KM_RUN_TIMED_STAGES)) {}
 };
 
+// ---- the step in pieces.  km_batch_run calls them in order on one stream; the paired pump (result_host.h) enqueues
+// them at different moments and on different streams: front (step_front: restore_layout, geometry, k_pack), middle
+// (step_seed: k_seed; step_walk: k_dfs_pure) and back (step_back: the large-tier launches, k_graph, the delivery).
+// What every run resets first.
+static void step_begin(km_batch* b, hipStream_t st, const RunFlags& f) {
+  b->last_stream = st;
+  if (f.stages & KM_STAGE_WALK) b->probes.count_fetches = f.count_fetches;
+  b->out.deliver_pending = b->out.result_ready = false;
+  b->tm.timed_deliver = false;
+  b->big.n_big = 0;
+}
+// Geometry of the step and the workspaces that follow from it.
+static int step_geometry(km_batch* b, const RunFlags& f) {
+  b->graph_mode = (f.stages & KM_STAGE_GRAPH) ? 0 : 1;
+  fast_geometry(b);
+  WalkArgs& wa = b->wa;
+  KMCHK(b->t.d_frames.alloc((uint64_t)b->n_targets * wa.f_stride));
+  KMCHK(ensure_bigdev_ws(b));
+  wa.f_ws = b->t.d_frames.p;
+  wa.stamps = nullptr;
+  if (knobs().seed_stamps) {
+    KMCHK(b->probes.d_stamps.alloc(16ull * (SEED_BLOCK / 64) * (b->in.n_items + 4)));
+    wa.stamps = b->probes.d_stamps.p;
+  }
+  b->tm.timed = f.timed;
+  b->tm.timed_fine = f.timed_fine;
+  return KM_OK;
+}
+// k_pack, the first kernel of a step (it also zeroes the path-pool counters of the graph kernels: no fill command)
+static int step_pack(km_batch* b, hipStream_t st) {
+  if (b->tm.timed) HIPCHK(hipEventRecord(b->tm.ev[0], st));
+  hipLaunchKernelGGL(k_pack, dim3((b->n_targets + PACK_WAVES - 1) / PACK_WAVES), dim3(64 * PACK_WAVES), 0, st, b->wa);
+  if (b->tm.timed && b->tm.timed_fine) HIPCHK(hipEventRecord(b->tm.ev[3], st));
+  return KM_OK;
+}
+// what a plain step (non-empty batch, walk stage) does before its first launch: afterwards its geometry is known
+static int step_open(km_batch* b, hipStream_t st, const RunFlags& f) {
+  step_begin(b, st, f);
+  restore_layout(b);
+  return step_geometry(b, f);
+}
+// front of a plain step on `st`
+static int step_front(km_batch* b, hipStream_t st, const RunFlags& f) {
+  KMCHK(step_open(b, st, f));
+  return step_pack(b, st);
+}
+static int step_seed(km_batch* b, hipStream_t st) {
+  if (b->in.n_items)
+    launch_seed(b->in.n_items, st, b->wa, b->probes.count_fetches);
+  if (b->tm.timed && b->tm.timed_fine) HIPCHK(hipEventRecord(b->tm.ev[4], st));
+  return KM_OK;
+}
+// May this step's k_dfs and k_graph_pure be one launch?  (the walk-only run's k_graph_pure answers nothing, ga.dbg;
+// the diagnostics measure k_dfs by itself)
+static bool step_fuses(const km_batch* b, const RunFlags& f) {
+  return knobs().fuse_pure && !f.serial && (f.stages & KM_STAGE_GRAPH) && b->ga.dbg == 0 && !knobs().dfs_replay &&
+         b->wa.stamps == nullptr && b->wa.dbg == 0 && fuses_pure(b);
+}
+// k_dfs (with k_graph_pure in its launch where step_fuses): *fused says which
+static int step_walk(km_batch* b, hipStream_t st, const RunFlags& f, bool* fused) {
+  WalkArgs& wa = b->wa;
+  GraphArgs& ga = b->ga;
+  // a batch's kernels run in ONE stream, in order: batches overlap with each other, every launch stream on a
+  // hardware queue of its own (see "streams" in host_common.h).  k_graph_pure needs nothing of k_dfs and runs
+  // beside it — rounds 2-3 on a side stream per batch, since round 6 as blocks of k_dfs's own launch;
+  // KM_RUN_SERIAL selects one launch each, k_graph_pure behind k_dfs.
+  ga.use_need_full = 1;
+  // diagnostics (KM_DFS_REPLAY=1|2): k_dfs twice, the SECOND launch is the one timed — its instruction
+  // cache is warm; with 2 a 1 GiB memset in between flushes L2 / Infinity Cache (data cold again)
+  const int dfs_replay = knobs().dfs_replay;
+  if (dfs_replay) {
+    launch_dfs(b, st, wa);
+    if (dfs_replay == 2) {
+      static void* scratch = nullptr;
+      if (!scratch) HIPCHK(hipMalloc(&scratch, 1ull << 30));
+      HIPCHK(hipMemsetAsync(scratch, 0, 1ull << 30, st));
+    }
+    if (b->tm.timed) HIPCHK(hipEventRecord(b->tm.ev[4], st));
+  }
+  *fused = step_fuses(b, f);
+  if (*fused) launch_dfs_pure(b, st, wa, ga);
+  else launch_dfs(b, st, wa);
+  HIPCHK(hipGetLastError());
+  if (b->tm.timed) HIPCHK(hipEventRecord(b->tm.ev[1], st));
+  return KM_OK;
+}
+// what follows the walk launch up to the end of the graph stage: [k_dfs of the device's large tier], k_graph_pure
+// unless it ran in k_dfs's launch, k_graph, [k_graph of the device's large tier]
+static int step_graph(km_batch* b, hipStream_t st, bool fused) {
+  b->big.bigdev_ran = b->big.big_entry && b->big.bigdev_armed;
+  KMCHK(launch_big_walk_dev(b, st));
+  if (!fused) launch_pure(b, st, b->ga);
+  launch_graph(b, st, b->ga);
+  KMCHK(launch_big_graph_dev(b, st));
+  HIPCHK(hipGetLastError());
+  b->ran_walk = true;
+  b->ran_graph = false;
+  return KM_OK;
+}
+// back of a plain step: step_graph and the delivery
+static int step_back(km_batch* b, hipStream_t st, const RunFlags& f, bool fused) {
+  KMCHK(step_graph(b, st, fused));
+  b->ran_graph = true;
+  b->synced = false;
+  return f.deliver ? enqueue_deliver(b, st, f.lean, f.count16) : KM_OK;
+}
+// middle and back of a plain step on `st`, its front enqueued there
+static int step_rest(km_batch* b, hipStream_t st, const RunFlags& f) {
+  bool fused = false;
+  KMCHK(step_seed(b, st));
+  KMCHK(step_walk(b, st, f, &fused));
+  return step_back(b, st, f, fused);
+}
+
+// The middle of TWO steps in one launch (graph_kernel.h: k_dfs_pure_seed): k_dfs and k_graph_pure of `prev`, whose
+// k_seed has run, and k_seed of `next`, whose k_pack is in front of this launch on `st`.  The caller has checked
+// that the two may share it (result_host.h: pairs_with).
+static int launch_dfs_pure_seed(km_batch* prev, km_batch* next, hipStream_t st) {
+  prev->ga.use_need_full = 1;
+  const uint32_t dfs_grid = prev->hints.dfs_grid(prev->n_targets), n_pure = prev->n_targets;
+  const uint64_t grid = (uint64_t)dfs_grid + n_pure + (uint64_t)(4 / SEED_WAVE_RUNS) * next->in.n_items;
+  if (grid > 0x7FFFFFFFull || prev->walk_lds < SEED_WAVE_LDS) return fail(KM_E_STATE, "paired launch out of range");
+  if (prev->wa.tab.k == 31)
+    hipLaunchKernelGGL((k_dfs_pure_seed<31>), dim3((uint32_t)grid), dim3(64), prev->walk_lds, st, prev->wa, prev->ga, dfs_grid, n_pure, next->wa);
+  else
+    hipLaunchKernelGGL((k_dfs_pure_seed<0>), dim3((uint32_t)grid), dim3(64), prev->walk_lds, st, prev->wa, prev->ga, dfs_grid, n_pure, next->wa);
+  HIPCHK(hipGetLastError());
+  return KM_OK;
+}
+
 // One step.  In stream order: k_pack (which also zeroes the path-pool counters), k_seed, k_dfs_pure (k_dfs and
 // k_graph_pure in one launch), [k_dfs of the device's large tier], k_graph, [k_graph of the device's large tier], then
 // the delivery (enqueue_deliver) when asked for.  With KM_RUN_SERIAL ("every kernel alone"), KM_FUSE_PURE=0, a
@@ -932,12 +1078,8 @@ extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
   ht[0] = host_trace ? host_now_us() : 0;
   HIPCHK(hipSetDevice(b->device));
   hipStream_t st = (hipStream_t)stream;
-  b->last_stream = st;
   const RunFlags f(stages);
-  if (f.stages & KM_STAGE_WALK) b->probes.count_fetches = f.count_fetches;
-  b->out.deliver_pending = b->out.result_ready = false;
-  b->tm.timed_deliver = false;
-  b->big.n_big = 0;
+  step_begin(b, st, f);
   if (!b->n_targets) {
     b->ran_walk = true;
     b->ran_graph = (f.stages & KM_STAGE_GRAPH) != 0;
@@ -957,23 +1099,9 @@ extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
     return f.deliver ? enqueue_deliver(b, st, f.lean, f.count16) : KM_OK;
   }
 
-  b->graph_mode = (f.stages & KM_STAGE_GRAPH) ? 0 : 1;
-  fast_geometry(b);
-  WalkArgs& wa = b->wa;
-  GraphArgs& ga = b->ga;
-  KMCHK(b->t.d_frames.alloc((uint64_t)b->n_targets * wa.f_stride));
-  KMCHK(ensure_bigdev_ws(b));
-  wa.f_ws = b->t.d_frames.p;
-  wa.stamps = nullptr;
-  if (knobs().seed_stamps) {
-    KMCHK(b->probes.d_stamps.alloc(16ull * (SEED_BLOCK / 64) * (b->in.n_items + 4)));
-    wa.stamps = b->probes.d_stamps.p;
-  }
-
+  KMCHK(step_geometry(b, f));
   bool graph_launched = false;
   // a captured step has no host round trips inside
-  b->tm.timed = f.timed;
-  b->tm.timed_fine = f.timed_fine;
   const bool capturing = f.hipgraph && st != nullptr && (f.stages & KM_STAGE_WALK);   // the NULL stream cannot be captured
   if (capturing) {
     b->tm.timed = false;
@@ -982,46 +1110,12 @@ extern "C" int km_batch_run(km_batch_t* b, int stages, void* stream) {
   }
   ht[2] = host_trace ? host_now_us() : 0;
   if (f.stages & KM_STAGE_WALK) {
-    // (the path-pool counters of the graph kernels are zeroed by k_pack: no fill command per step)
-    if (b->tm.timed) HIPCHK(hipEventRecord(b->tm.ev[0], st));
-    hipLaunchKernelGGL(k_pack, dim3((b->n_targets + PACK_WAVES - 1) / PACK_WAVES), dim3(64 * PACK_WAVES), 0, st, wa);
-    if (b->tm.timed && f.timed_fine) HIPCHK(hipEventRecord(b->tm.ev[3], st));
-    if (b->in.n_items)
-      launch_seed(b->in.n_items, st, wa, b->probes.count_fetches);
-    if (b->tm.timed && f.timed_fine) HIPCHK(hipEventRecord(b->tm.ev[4], st));
-    // a batch's kernels run in ONE stream, in order: batches overlap with each other, every launch stream on a
-    // hardware queue of its own (see "streams" in host_common.h).  k_graph_pure needs nothing of k_dfs and runs
-    // beside it — rounds 2-3 on a side stream per batch, since round 6 as blocks of k_dfs's own launch;
-    // KM_RUN_SERIAL selects one launch each, k_graph_pure behind k_dfs.
-    ga.use_need_full = 1;
-    // diagnostics (KM_DFS_REPLAY=1|2): k_dfs twice, the SECOND launch is the one timed — its instruction
-    // cache is warm; with 2 a 1 GiB memset in between flushes L2 / Infinity Cache (data cold again)
-    const int dfs_replay = knobs().dfs_replay;
-    if (dfs_replay) {
-      launch_dfs(b, st, wa);
-      if (dfs_replay == 2) {
-        static void* scratch = nullptr;
-        if (!scratch) HIPCHK(hipMalloc(&scratch, 1ull << 30));
-        HIPCHK(hipMemsetAsync(scratch, 0, 1ull << 30, st));
-      }
-      if (b->tm.timed) HIPCHK(hipEventRecord(b->tm.ev[4], st));
-    }
-    // (the walk-only run's k_graph_pure answers nothing, ga.dbg; the diagnostics measure k_dfs by itself)
-    const bool fused = knobs().fuse_pure && !f.serial && (f.stages & KM_STAGE_GRAPH) && ga.dbg == 0 && !dfs_replay &&
-                       wa.stamps == nullptr && wa.dbg == 0 && fuses_pure(b);
-    if (fused) launch_dfs_pure(b, st, wa, ga);
-    else launch_dfs(b, st, wa);
-    HIPCHK(hipGetLastError());
-    if (b->tm.timed) HIPCHK(hipEventRecord(b->tm.ev[1], st));
-    b->big.bigdev_ran = b->big.big_entry && b->big.bigdev_armed;
-    KMCHK(launch_big_walk_dev(b, st));
-    if (!fused) launch_pure(b, st, ga);
-    launch_graph(b, st, ga);
-    KMCHK(launch_big_graph_dev(b, st));
-    HIPCHK(hipGetLastError());
+    bool fused = false;
+    KMCHK(step_pack(b, st));
+    KMCHK(step_seed(b, st));
+    KMCHK(step_walk(b, st, f, &fused));
+    KMCHK(step_graph(b, st, fused));
     graph_launched = true;
-    b->ran_walk = true;
-    b->ran_graph = false;
   } else if (!b->ran_walk) {
     return fail(KM_E_STATE, "graph stage requested before the walk stage");
   } else {

@@ -301,6 +301,31 @@ void k_dfs_pure(WalkArgs wa, GraphArgs ga, uint32_t n_dfs_blocks) {
   dfs_body<false, K>(wa, blockIdx.x, n_dfs_blocks);
 }
 
+// ... and k_seed of the NEXT batch in the same launch (the paired pump, result_host.h): behind the previous batch's
+// walk blocks [0, n_dfs_blocks) and its n_pure_blocks pure-chain blocks, block n_dfs_blocks + n_pure_blocks + item runs
+// seed_body (walk_kernel.h) for item record `item` of the next batch: one wave for the item's 256 seeds, four per lane
+// with their load chains in flight together (a wave of this launch has 128 vector registers and a SIMD holds four of
+// them, half of k_seed's eight: with one seed per lane the launch took as long as the two kernels one after the
+// other).  k_seed needs all the memory system gives and k_dfs waits on its slowest
+// wave's dependent round trips: the seed waves fill the wave slots and the bandwidth the long walks leave.  The roles of
+// the two batches share nothing but the read-only table, and no role waits for another — no flag, no spin, no ticket:
+// any block may run before or after any other.  The dynamic LDS is the previous batch's k_dfs's (at least
+// SEED_WAVE_LDS: its node set alone is 2 560 bytes).
+template <int K>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES_PER_EU)))
+void k_dfs_pure_seed(WalkArgs wa_prev, GraphArgs ga_prev, uint32_t n_dfs_blocks, uint32_t n_pure_blocks, WalkArgs wa_next) {
+  if (blockIdx.x >= n_dfs_blocks + n_pure_blocks) {
+    const uint32_t s = blockIdx.x - n_dfs_blocks - n_pure_blocks;
+    seed_body<K, false, SEED_WAVE_RUNS>(wa_next, s / (4 / SEED_WAVE_RUNS), s % (4 / SEED_WAVE_RUNS));
+    return;
+  }
+  if (blockIdx.x >= n_dfs_blocks) {
+    pure_body<K>(ga_prev, blockIdx.x - n_dfs_blocks);
+    return;
+  }
+  dfs_body<false, K>(wa_prev, blockIdx.x, n_dfs_blocks);
+}
+
 // Direct mode (large tier, a.tids given): block b works on target tids[b].  LDS tier: block b
 // works on entry b of the work list (GraphArgs::work_list) — the blocks that have something to do
 // are the first ones of the grid and are dispatched together; the others leave after one load

@@ -138,17 +138,193 @@ extern "C" int km_batch_result(km_batch_t* b, km_batch_out_t* view, km_batch_siz
 // delivery is awaited (km_batch_result), at the end every batch's.  The loop a pipelined consumer
 // writes, kept on the library's side of the ABI so that an interpreter between two launches does
 // not sit in the timed region (diagnostics / bench; tools/launch_cost.py).
+//
+// Consecutive steps are PAIRED where they can be: k_seed of the next batch runs as blocks of the previous batch's
+// k_dfs_pure launch (graph_kernel.h: k_dfs_pure_seed), so that the two kernels that are three quarters of a step's
+// chain — one bound by memory, one by its slowest wave — overlap whatever the streams' hardware queues do.  The
+// paired steps use TWO streams of the pump's own (pool streams held for the call), whatever n is.  The chain —
+// k_pack(next), the paired launch, k_pack, the paired launch, ... — goes to one, where each command follows the last
+// without a wait between two queues; behind every paired launch an event is recorded, and the other stream, the
+// tail, waits for it and takes the back of the walked batch's step (large tier, k_graph, delivery), off the chain.
+// (With the chain on the batches' own streams, each paired launch behind an event of the stream before it, the GPU
+// stood idle a fifth of the time; with the backs on the batches' own streams the chain shared hardware queues with
+// their copies: DESIGN.md section 5, round 7.)  The chain waits once for what the caller has put on a batch's stream
+// before the call; when the pump returns every delivery has been awaited and a batch's stream is its own again.
+// The first step of a run of paired steps seeds with the block k_seed, the last one walks with k_dfs_pure.  A step
+// that cannot be paired is km_batch_run's sequence on the batch's own stream; KM_PUMP_UNPAIRED or KM_PAIR_SEED=0:
+// every step is.
+//
+// One chain gives up the overlap of n streams, so by default a step is paired only where that trade pays
+// (pairing_pays, seeds_fill_device below; the figures: DESIGN.md section 5, round 7): at most PAIR_MAX_BATCHES batches
+// in flight, a lean delivery, and seeds of the next batch for PAIR_MIN_SEED_ROUNDS rounds of the device.
+// KM_PUMP_PAIRED or KM_PAIR_SEED=2 pairs every step that CAN be paired (tests, measurements).
+
+// May steps with these flags be paired at all?  Plain walk + graph + delivery, no diagnostics.
+static bool pairing_allowed(int n, int stages) {
+  const int plain = KM_STAGE_WALK | KM_STAGE_GRAPH | KM_RUN_DELIVER | KM_DELIVER_LEAN | KM_DELIVER_COUNT16;
+  const int must = KM_STAGE_WALK | KM_STAGE_GRAPH | KM_RUN_DELIVER;
+  return n >= 2 && (stages & ~plain) == 0 && (stages & must) == must && knobs().pair_seed != 0 && knobs().fuse_pure &&
+         !knobs().seed_stamps && !knobs().dfs_replay && knobs().debug_flags == 0;
+}
+// May k_seed of `next` run in the walk launch of `prev`?  (What does not change between two km_batch_set_targets.)
+static bool pairs_with(const km_batch* prev, const km_batch* next) {
+  // (the paired launch's grid: at most n_targets walk blocks + n_targets pure-chain blocks + the seed blocks)
+  const uint64_t grid_max = 2ull * prev->n_targets + (uint64_t)(4 / SEED_WAVE_RUNS) * next->in.n_items;
+  return prev != next && prev->device == next->device && prev->n_targets && next->n_targets && next->in.n_items &&
+         (prev->db->k == 31) == (next->db->k == 31) && grid_max <= 0x7FFFFFFFull;
+}
+
+// Does the walk launch of `b` (front enqueued: its geometry is known) take another batch's seeds?  Its k_dfs and
+// k_graph_pure must share a launch, and its walk blocks — the grid follows the flagged targets of b's last delivery —
+// must all be resident at once (CU_SIMDS x KM_DFS_WAVES_PER_EU = 16 waves per CU at 128 registers, fewer where a block's
+// share of the CU's LDS says so): every seed block then starts as soon as a walk wave retires.  A walk that needs several rounds of the device has no idle slot
+// before its last round; the seeds would only be appended to it, and the one chain of the paired steps would cost the
+// overlap of the batches' walks on their own streams (measured on the workload whose every target is flagged, 10 000
+// walk blocks: 0.71 ms per step unpaired, 1.15 paired: DESIGN.md section 5, round 7).
+constexpr uint32_t CU_SIMDS = 4;               // SIMDs of a CDNA compute unit
+constexpr uint32_t CU_LDS_BYTES = 160u << 10;  // LDS of a gfx950 compute unit
+static bool takes_seeds(const km_batch* b, const RunFlags& f, int cus) {
+  const uint64_t per_cu = std::min<uint64_t>(CU_SIMDS * KM_DFS_WAVES_PER_EU, CU_LDS_BYTES / std::max<uint32_t>(b->walk_lds, 1u));
+  return step_fuses(b, f) && b->walk_lds >= SEED_WAVE_LDS &&      // (a seed wave's key windows are part of the launch's LDS)
+         (uint64_t)b->hints.dfs_grid(b->n_targets) <= per_cu * (uint64_t)cus;
+}
+
+// Does pairing pay for a pump of n batches with these flags?  The paired steps share ONE chain stream and one tail
+// stream.  That is a gain where the GPU is the limit and the chain's two long kernels are what a step costs; it is a
+// loss where the consumer answers a latency-bound step with more batches in flight than the four the gain was
+// measured with (8 batches of 1 250-5 000 targets: 1.4-2.1 x slower paired), and where the delivery copy is
+// what a step costs (a full delivery, 20 MB per step: every copy and the delivery kernels of the step behind it
+// follow each other on the tail, 0.454 -> 0.488 ms per step paired).
+constexpr int PAIR_MAX_BATCHES = 4;
+static bool pairing_pays(int n, const RunFlags& f) { return n <= PAIR_MAX_BATCHES && f.lean; }
+// ... and for this next batch?  Its seed blocks must fill the wave slots of the walk launch (CU_SIMDS x
+// KM_DFS_WAVES_PER_EU per compute unit) PAIR_MIN_SEED_ROUNDS times over: only then is the seed role bound by the
+// memory system, whose idle share under the walk is what the paired launch wins.  Fewer seed waves wait for their own
+// dependent loads like the walk beside them, the step is bound by the latency of its chain of kernels, and n chains on
+// n streams are shorter than one (4 batches of 1 250 targets x 500 nt, 0.6 rounds: 0.070 -> 0.077 ms per step paired).
+constexpr uint32_t PAIR_MIN_SEED_ROUNDS = 2;
+static bool seeds_fill_device(const km_batch* next, int cus) {
+  return (uint64_t)(4 / SEED_WAVE_RUNS) * next->in.n_items >=
+         (uint64_t)PAIR_MIN_SEED_ROUNDS * CU_SIMDS * KM_DFS_WAVES_PER_EU * (uint64_t)cus;
+}
+
 extern "C" int km_batch_pump(km_batch_t* const* bs, void* const* streams, int n, int steps, int stages) {
   if (!bs || n <= 0 || steps < 0) return fail(KM_E_ARG, "bad argument");
   const bool deliver = (stages & KM_RUN_DELIVER) != 0;
+  const bool wherever = (stages & KM_PUMP_PAIRED) || knobs().pair_seed == 2;   // not only where it pays
+  const bool unpaired = (stages & KM_PUMP_UNPAIRED) != 0;
+  stages &= ~(KM_PUMP_UNPAIRED | KM_PUMP_PAIRED);
+  const RunFlags f(stages);
+  const bool may_pair = !unpaired && pairing_allowed(n, stages) && (wherever || pairing_pays(n, f));
+  CallStream chain, tail;                // the streams of the paired steps (taken at the first such step)
+  int chain_device = -1;                 // their device
+  int cus = 0, cus_device = -1;          // the compute units of the device of the batch at hand
+  auto learn_cus = [&](int device) -> int {
+    if (device != cus_device) HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    cus_device = device;
+    return KM_OK;
+  };
+  // may k_seed of `next` run in the walk launch of `prev`, and is it worth it?
+  auto pairs = [&](const km_batch* prev, const km_batch* next) {
+    return pairs_with(prev, next) && (wherever || seeds_fill_device(next, cus));
+  };
+  km_batch* prev = nullptr;              // front and k_seed enqueued on the chain, the rest of its step not yet
+  // However the call ends, no batch keeps a stream of the pump's as its last_stream: on success every delivery has
+  // been awaited; on an error return the two streams are waited for first.  (Declared behind `chain` and `tail`: it
+  // runs before they are given back.)
+  struct GiveBack {
+    km_batch_t* const* bs; void* const* streams; int n; const CallStream &chain, &tail; bool ok = false;
+    ~GiveBack() {
+      for (int q = 0; q < n; ++q) {
+        km_batch* b = bs[q];
+        if (!b || !b->pair.borrowed) continue;
+        if (!ok) {
+          (void)hipSetDevice(b->device);
+          if (chain.st) (void)hipStreamSynchronize(chain);
+          if (tail.st) (void)hipStreamSynchronize(tail);
+        }
+        b->last_stream = (hipStream_t)(streams ? streams[q] : nullptr);
+        b->pair.borrowed = false;
+      }
+    }
+  } give_back{bs, streams, n, chain, tail};
+  // prev's walk launch is on the chain: the tail takes the back of its step behind it
+  auto back_of_prev = [&](bool fused) -> int {
+    if (!prev->pair.ev_walked) HIPCHK(hipEventCreateWithFlags(&prev->pair.ev_walked.h, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(prev->pair.ev_walked, chain));
+    HIPCHK(hipStreamWaitEvent(tail, prev->pair.ev_walked, 0));
+    prev->last_stream = tail;
+    return step_back(prev, tail, f, fused);
+  };
+  // the rest of prev's step without another batch's seeds: k_dfs_pure, the back
+  auto finish_alone = [&]() -> int {
+    bool fused = false;
+    HIPCHK(hipSetDevice(prev->device));
+    KMCHK(step_walk(prev, chain, f, &fused));
+    KMCHK(back_of_prev(fused));
+    prev = nullptr;
+    return KM_OK;
+  };
+  // b's step goes to the pump's streams: behind its un-awaited run of before this pump, if any, and behind what
+  // the caller has put on its stream
+  auto borrow = [&](km_batch* b, hipStream_t st, bool first_round) -> int {
+    KMCHK(wait_in_flight(b));
+    if (first_round) {
+      if (!b->pair.ev_walked) HIPCHK(hipEventCreateWithFlags(&b->pair.ev_walked.h, hipEventDisableTiming));
+      HIPCHK(hipEventRecord(b->pair.ev_walked, st));
+      HIPCHK(hipStreamWaitEvent(chain, b->pair.ev_walked, 0));
+    }
+    b->pair.borrowed = true;
+    return KM_OK;
+  };
   for (int i = 0; i < steps; ++i) {
     km_batch_t* b = bs[i % n];
+    hipStream_t st = (hipStream_t)(streams ? streams[i % n] : nullptr);
     if (i >= n && deliver) KMCHK(finish_result(b, false));
-    KMCHK(km_batch_run(b, stages, streams ? streams[i % n] : nullptr));
+    if (may_pair) KMCHK(learn_cus(b->device));
+    if (prev && pairs(prev, b)) {
+      HIPCHK(hipSetDevice(b->device));
+      KMCHK(borrow(b, st, i < n));
+      KMCHK(step_front(b, chain, f));
+      KMCHK(launch_dfs_pure_seed(prev, b, chain));
+      ++b->pair.n_seeded;
+      KMCHK(back_of_prev(true));
+      // (can b, in its turn, take the seeds of the step after it?  Its geometry is known now.)
+      prev = b;
+      if (!takes_seeds(b, f, cus)) KMCHK(finish_alone());
+      continue;
+    }
+    if (prev) KMCHK(finish_alone());
+    const bool first_of_pair = may_pair && i + 1 < steps && pairs(b, bs[(i + 1) % n]) &&
+                               (chain_device < 0 || chain_device == b->device);
+    if (!first_of_pair) {
+      KMCHK(km_batch_run(b, stages, st));
+      continue;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    KMCHK(wait_in_flight(b));              // (an un-awaited run of before this pump, on whichever stream)
+    KMCHK(step_open(b, st, f));
+    if (!takes_seeds(b, f, cus)) {         // its walk takes nobody's seeds: the whole step on its own stream
+      KMCHK(step_pack(b, st));
+      KMCHK(step_rest(b, st, f));
+      continue;
+    }
+    if (chain_device < 0) {
+      KMCHK(chain.get(b->device, nullptr));
+      KMCHK(tail.get(b->device, nullptr));
+      chain_device = b->device;
+    }
+    KMCHK(borrow(b, st, i < n));
+    b->last_stream = chain;
+    KMCHK(step_pack(b, chain));
+    KMCHK(step_seed(b, chain));
+    prev = b;
   }
+  if (prev) KMCHK(finish_alone());
   for (int q = 0; q < std::min(n, steps); ++q) {
     KMCHK(deliver ? finish_result(bs[q], false) : km_batch_sync(bs[q]));
   }
+  give_back.ok = true;                   // nothing of any batch is left on the pump's streams
   return KM_OK;
 }
 
@@ -274,6 +450,7 @@ extern "C" int km_batch_debug_counts(km_batch_t* b, uint32_t* out4) {
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipStreamSynchronize(b->last_stream));
   HIPCHK(hipMemcpy(out4, b->t.d_nflagged.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  out4[3] = b->pair.n_seeded;
   return KM_OK;
 }
 

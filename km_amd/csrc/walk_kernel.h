@@ -584,6 +584,203 @@ __global__ __launch_bounds__(SEED_BLOCK) void k_seed(WalkArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------- seed_body
+// k_seed's work at WAVE granularity, for launches whose blocks are single waves (graph_kernel.h: k_dfs_pure_seed, where
+// the seeds of the NEXT batch run as blocks of the previous batch's walk launch; k_seed_waves below, for the record).
+// An item record's 256 seeds are four runs of 64; a wave takes NS of them, lane l the seeds 64 (wave + (4 / NS) j) + l
+// for j < NS (NS = 1: one run per wave, four waves per item; NS = 2: runs `wave` and `wave + 2`, two waves per item;
+// NS = 4, SEED_WAVE_RUNS, what the launches use: the whole item).  Inside the walk launch a wave has 128 vector registers
+// and a SIMD holds four waves, not k_seed's eight: with NS runs a lane has the load chains of NS seeds in flight
+// together, which gives the memory system back the requests that the missing waves would have issued (the paired
+// launch alone, round 7: 162.4 us with NS = 1, 143.5 with 2, 132.5 with 4, against k_seed 77.2 + k_dfs_pure 75.7 = 152.9 one
+// after the other in the same session).  No barrier: the wave hashes its own 64 + w selection keys per run (lanes < w a
+// second m-mer) into its own windows at the start of the launch's dynamic LDS and reads them back behind a wait for
+// its own LDS operations, as k_pack does for its words.  Everything else is k_seed's, with `tid` the seed's index in the
+// item: the head lane and its use of the key of base 0, the exit on a target that cannot be walked, node_cnt of seed
+// i + 1, the flag record, one atomic pair per wave.  A wave none of whose seeds exists (all past the target's last
+// k-mer) stores nothing in k_seed either and leaves after the header.
+constexpr uint32_t SEED_WAVE_KEYS = 96;                      // 64 + w keys, w <= 32
+constexpr int SEED_WAVE_RUNS = 4;                            // NS of the launches
+constexpr uint32_t SEED_WAVE_LDS = SEED_WAVE_RUNS * SEED_WAVE_KEYS * 4;   // bytes of dynamic LDS a seed wave needs
+template <int K, bool FETCHES, int NS>
+__device__ __forceinline__ void seed_body(const WalkArgs a, const uint32_t item, const uint32_t wave) {
+  static_assert(SEED_BLOCK == 256, "the item record holds 12 words = 256 seeds + k - 1 + 1 bases");
+  static_assert(NS == 1 || NS == 2 || NS == 4, "one, two or all four runs of 64 seeds per wave");
+  constexpr uint32_t WAVES = 4 / NS;                         // waves per item
+  extern __shared__ __align__(16) unsigned char smem[];
+  uint32_t* const raw_all = reinterpret_cast<uint32_t*>(smem);   // run j: raw_all[96 j + q] = selection key of the m-mer at item base tid[j] - lane + q
+  const TableView tab = specialized_view<K>(a.tab);
+  const int k = tab.k;
+  const uint32_t lane = (uint32_t)lane_id();
+  const uint32_t W = (uint32_t)tab.w;
+  const uint64_t* rec = a.items + 16ull * item;
+  auto bits_at = [&](uint32_t q) -> uint64_t {
+    const uint32_t w = q >> 5, sh = (q & 31) * 2;
+    const uint64_t hi = rec[4 + w], lo = rec[5 + w];
+    return (hi << sh) | ((lo >> 1) >> (63 - sh));
+  };
+  // (one struct per run and every phase a call per run, not arrays in loops: those stayed in scratch memory)
+  struct Run {
+    uint32_t tid, m_rest, u_child, S, pos;
+    uint64_t x, X;
+    Key g;
+    DirPair dw;
+    const Slot* base;
+    uint4 first, second;
+  };
+  Run r0, r1, r2, r3;
+  auto hash_keys = [&](Run& r, const uint32_t j) {
+    r.tid = 64u * (wave + WAVES * j) + lane;
+    r.x = bits_at(r.tid);
+    uint32_t* raw = raw_all + SEED_WAVE_KEYS * j;
+    raw[lane] = mmer_scan_key(tab, r.x, r.tid);
+    if (lane < W) raw[64 + lane] = mmer_scan_key(tab, bits_at(r.tid + 64), r.tid + 64);
+  };
+  hash_keys(r0, 0);
+  if constexpr (NS >= 2) hash_keys(r1, 1);
+  if constexpr (NS == 4) { hash_keys(r2, 2); hash_keys(r3, 3); }
+  const uint64_t h0 = rec[0], h1 = rec[1];
+  const uint64_t nb = rec[2], fwo = rec[3] & 0xFFFFFFFFull;
+  const uint32_t wo32 = (uint32_t)(rec[3] >> 32);
+  if ((uint32_t)(h1 >> 32) == 0u) return;                  // target not walkable (status != OK); wave-uniform
+  const uint32_t t = (uint32_t)h0;
+  const uint32_t n_ref = (uint32_t)h1;
+  const uint32_t i_first = (uint32_t)(h0 >> 32);           // the item's first seed, a multiple of 256
+  if (i_first + 64u * wave >= n_ref) return;               // no seed of this wave exists (its first run is the lower one); wave-uniform
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // one wave: LDS runs its operations in order
+  auto minimizer = [&](Run& r, const uint32_t j) {
+    const uint32_t* w = raw_all + SEED_WAVE_KEYS * j + lane + 1;
+    uint32_t m_last;                                       // key of base tid+w; m_rest: min over bases tid+1 .. tid+w-1
+    if (W == 16) {
+      const uint32_t m0 = min(min(w[0], w[1]), w[2]), m1 = min(min(w[3], w[4]), w[5]);
+      const uint32_t m2 = min(min(w[6], w[7]), w[8]), m3 = min(min(w[9], w[10]), w[11]);
+      const uint32_t m4 = min(min(w[12], w[13]), w[14]);
+      r.m_rest = min(min(min(m0, m1), m2), min(m3, m4));
+      m_last = w[15];
+    } else {
+      r.m_rest = ~0u;
+      for (uint32_t q = 1; q < W; ++q) r.m_rest = min(r.m_rest, w[q - 1]);
+      m_last = w[W - 1];
+    }
+    r.u_child = (min(r.m_rest, m_last) & SEL_POS) - (r.tid + 1);
+  };
+  minimizer(r0, 0);
+  if constexpr (NS >= 2) minimizer(r1, 1);
+  if constexpr (NS == 4) { minimizer(r2, 2); minimizer(r3, 3); }
+
+  // ---- key, directory word, home pair of every run, requested together; the head lane (seed 0 of the target: lane 0
+  // of wave 0 of its first item, run 0, whose window starts at base 0) also needs query(ref[0])
+  auto directory = [&](Run& r) {
+    r.X = r.x >> (64 - 2 * k);
+    r.g = key_from_window(tab, r.X & tab.pmask, r.u_child);
+    r.dw = *reinterpret_cast<const DirPair*>(tab.dir + r.g.bucket);
+  };
+  directory(r0);
+  if constexpr (NS >= 2) directory(r1);
+  if constexpr (NS == 4) { directory(r2); directory(r3); }
+  const bool head = i_first + r0.tid == 0;
+  Key gq = r0.g;
+  DirPair dq = r0.dw;
+  if (head) {
+    const uint32_t u_first = min(raw_all[0], r0.m_rest) & SEL_POS;
+    gq = key_from_window(tab, r0.X >> 2, u_first);
+    dq = *reinterpret_cast<const DirPair*>(tab.dir + gq.bucket);
+  }
+  auto home_pair = [&](Run& r) {
+    r.S = (uint32_t)bucket_slots(r.dw.lo, r.dw.hi);
+    r.base = tab.slots + 2ull * r.dw.lo;
+    r.pos = (uint32_t)home_slot(tab, r.g, r.S);            // 0 for an empty bucket
+    // loaded unconditionally (an empty bucket reads some valid slots and ignores them)
+    const Slot* b0 = (r.S ? r.base : tab.slots) + r.pos;
+    r.first = *reinterpret_cast<const uint4*>(b0);
+    r.second = *reinterpret_cast<const uint4*>(b0 + 1);
+  };
+  home_pair(r0);
+  if constexpr (NS >= 2) home_pair(r1);
+  if constexpr (NS == 4) { home_pair(r2); home_pair(r3); }
+  uint32_t Sq = 0, posq = 0;
+  const Slot* baseq = tab.slots;
+  uint4 firstq = r0.first, secondq = r0.second;
+  if (head) {
+    Sq = (uint32_t)bucket_slots(dq.lo, dq.hi);
+    baseq = tab.slots + 2ull * dq.lo;
+    posq = (uint32_t)home_slot(tab, gq, Sq);
+    const Slot* bq = (Sq ? baseq : tab.slots) + posq;
+    firstq = *reinterpret_cast<const uint4*>(bq);
+    secondq = *reinterpret_cast<const uint4*>(bq + 1);
+  }
+
+  unsigned long long probes_w = 0, fetch_w = 0;
+  auto classify = [&](Run& r, const bool with_head) {
+    const uint32_t i = i_first + r.tid;
+    uint32_t fetch_l = 0;
+    bool valid = false, triv = false, triv_child = false;
+    if (i < n_ref) {
+      valid = true;
+      uint4 c4 = make_uint4(0, 0, 0, 0);
+      if (r.S) c4 = bucket_resolve2(tab, r.g, r.base, r.S, r.pos, r.first, r.second, &fetch_l);
+      c4 = finish_children(tab, r.X, r.g.flip, c4);
+      uint32_t nextb = 4;
+      if (i + 1 < n_ref) {
+        // last base of ref[i+1] = base k of this lane's 32-base window (k <= 31), else reloaded
+        if (k < 32) {
+          nextb = (uint32_t)(r.x >> (62 - 2 * k)) & 3u;
+        } else {
+          const uint32_t p = r.tid + (uint32_t)k;
+          nextb = (uint32_t)(rec[4 + (p >> 5)] >> (62 - 2 * (p & 31))) & 3u;
+        }
+        a.node_cnt[nb + i + 1] = pick4(c4, nextb);
+      }
+      if (with_head && head) {                             // node_data[ref[0]] = jf.query(ref[0])
+        uint4 cq = make_uint4(0, 0, 0, 0);
+        if (Sq) cq = bucket_resolve2(tab, gq, baseq, Sq, posq, firstq, secondq, &fetch_l);
+        const uint32_t sb = (uint32_t)(r.X & 3);
+        uint32_t v = pick4(cq, gq.flip ? 3 - sb : sb);
+        if (v == COUNT_ESCAPE) v = overflow_count(tab, r.X);
+        a.node_cnt[nb] = v;
+      }
+      if (a.max_stack > 0) {
+        const uint32_t mask = child_mask(c4, a.ratio, a.nc);
+        triv = (mask == 0) || (nextb < 4 && mask == (1u << nextb));
+        triv_child = triv && mask != 0;
+        if (!triv) {
+          atomicOr(&a.flagbits[fwo + (i >> 5)], 1u << (i & 31));
+          if (atomicExch(&a.tflag[t], 1u) == 0u) {
+            const uint32_t at = atomicAdd(a.n_flagged, 1u);
+            a.flagged[at] = t;
+            a.flag_rec[2 * at] = make_uint4(t, n_ref, (uint32_t)nb, (uint32_t)(nb >> 32));
+            a.flag_rec[2 * at + 1] = make_uint4((uint32_t)fwo, wo32, 0u, 0u);
+          }
+        }
+      }
+    }
+    // the per-target counters, as in k_seed
+    probes_w += (unsigned long long)__popcll(__ballot(valid)) + 4ull * __popcll(__ballot(triv)) + __popcll(__ballot(triv_child));
+    if constexpr (FETCHES) {
+      fetch_w += (unsigned long long)__popcll(__ballot(fetch_l >= 1)) + __popcll(__ballot(fetch_l >= 2));
+      if (__any(fetch_l > 2)) {
+        uint32_t extra = fetch_l > 2 ? fetch_l - 2 : 0;
+        for (int o = 32; o > 0; o >>= 1) extra += __shfl_xor(extra, o);
+        fetch_w += extra;
+      }
+    }
+  };
+  classify(r0, true);
+  if constexpr (NS >= 2) classify(r1, false);
+  if constexpr (NS == 4) { classify(r2, false); classify(r3, false); }
+  if (lane == 0 && probes_w) {                             // one atomic pair per wave
+    atomicAdd(&a.probes[t], probes_w);
+    if constexpr (FETCHES) atomicAdd(&a.fetches[t], fetch_w);
+  }
+}
+
+// k_seed as single-wave blocks (KM_SEED_WAVES=1: what seed_body costs alone; results unchanged): block (4 / NS) item + w
+template <int K>
+__global__ __launch_bounds__(64) void k_seed_waves(WalkArgs a) {
+  constexpr uint32_t WAVES = 4 / SEED_WAVE_RUNS;
+  seed_body<K, false, SEED_WAVE_RUNS>(a, blockIdx.x / WAVES, blockIdx.x % WAVES);
+}
+
 // ---------------------------------------------------------------------------- k_dfs
 // Diagnostics: -DKM_DFS_COUNTERS (tools/dfs_lifetimes.py with DFS_COUNTERS=1) counts and times, per wave, what the
 // walk did (the KM_DC / KM_DT macros below; nothing in the product build).  KM_SEED_STAMPS in the environment records

@@ -24,6 +24,8 @@ KM_DELIVER_COUNT16 = 128        # node counts cross PCIe as 16-bit values + the 
 KM_RUN_COUNT_FETCHES = 256      # count the table slots read (sizes.table_fetches; a diagnostic, 2 % of a step)
 KM_RUN_SERIAL = 64
 KM_RUN_TIMED_STAGES = 512       # with KM_RUN_TIMED: stage boundaries only (no event records between the walk stage's kernels)
+KM_PUMP_UNPAIRED = 1024         # km_batch_pump: every step is km_batch_run's own sequence (no k_seed in another batch's walk launch)
+KM_PUMP_PAIRED = 2048           # km_batch_pump: pair every step that can be paired, not only where it pays (<= 4 batches, lean delivery, large batches)
 T_OK, T_NODE_LIMIT, T_REPEAT_KMER, T_EMPTY, T_BAD_BASE, T_INTERNAL = range(6)
 
 # every symbol include/kmgpu.h declares (tests check the library exports them all)
@@ -987,6 +989,12 @@ class Batch:
         out = (C.c_uint32 * 4)()
         check(self._lib.km_batch_debug_counts(self._b, out))
         return int(out[0]), int(out[1]), int(out[2])
+
+    def paired_steps(self):
+        """How often, since the batch was made, its k_seed has run in another batch's walk launch (km_batch_pump)."""
+        out = (C.c_uint32 * 4)()
+        check(self._lib.km_batch_debug_counts(self._b, out))
+        return int(out[3])
 
     def debug_stamps(self):
         """k_seed time stamps (KM_SEED_STAMPS diagnostics): uint64 array [n_waves, 16]."""

@@ -117,11 +117,14 @@ int main(int argc, char** argv) {
   std::vector<void*> streams((size_t)n_fl, nullptr);
   for (int q = 0; q < n_fl; ++q) {
     CHECK(km_batch_create(db, &prm, T, (uint64_t)T * L, &bs[(size_t)q]));
-    CHECK(km_stream_create(0, &streams[(size_t)q]));
+    // KMCLIENT_ONE_STREAM: every batch on the first batch's stream — nothing overlaps a launch (kernels alone)
+    if (q > 0 && getenv("KMCLIENT_ONE_STREAM")) streams[(size_t)q] = streams[0];
+    else CHECK(km_stream_create(0, &streams[(size_t)q]));
     CHECK(km_batch_set_targets(bs[(size_t)q], ascii.data() + (uint64_t)q * T * L, off.data(), T));
   }
   const int flags = KM_STAGE_WALK | KM_STAGE_GRAPH | KM_RUN_DELIVER | KM_DELIVER_LEAN |
-                    (getenv("KMCLIENT_COUNT32") ? 0 : KM_DELIVER_COUNT16);
+                    (getenv("KMCLIENT_COUNT32") ? 0 : KM_DELIVER_COUNT16) |
+                    (getenv("KMCLIENT_UNPAIRED") ? KM_PUMP_UNPAIRED : 0) | (getenv("KMCLIENT_PAIRED") ? KM_PUMP_PAIRED : 0);
 
   if (mode == "pump") {
     CHECK(km_batch_pump(bs.data(), streams.data(), n_fl, warmup > n_fl ? warmup : n_fl, flags));
@@ -258,7 +261,7 @@ int main(int argc, char** argv) {
   }
   for (int q = 0; q < n_fl; ++q) {
     CHECK(km_batch_destroy(bs[(size_t)q]));
-    CHECK(km_stream_destroy(streams[(size_t)q]));
+    if (q == 0 || streams[(size_t)q] != streams[0]) CHECK(km_stream_destroy(streams[(size_t)q]));
   }
   CHECK(kmjf_close(db));
   return 0;

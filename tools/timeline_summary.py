@@ -38,8 +38,16 @@ for r in rows("*memory_copy_trace.csv"):
                    col(r, "Stream_Id", "Queue_Id") or "?"))
 kern.sort()
 copies.sort()
-# (k_dfs_pure: k_dfs and k_graph_pure as one launch, the default since round 6 — a step then has six kernels, not seven)
-ours = ("k_pack", "k_seed", "k_dfs", "k_dfs_pure", "k_graph_pure", "k_graph", "k_out_scan", "k_out_pack")
+# (k_dfs_pure: k_dfs and k_graph_pure as one launch, the default since round 6 — a step then has six kernels, not seven.
+# k_dfs_pure_seed, round 7's paired pump: that launch with k_seed of the NEXT batch in it.  What a stream then shows
+# between two k_pack is k_pack of the next batch, the paired launch, and the back and the copy of the PREVIOUS batch —
+# five kernels, the span of one step of the pump all the same)
+ours = ("k_pack", "k_seed", "k_dfs", "k_dfs_pure", "k_dfs_pure_seed", "k_graph_pure", "k_graph", "k_out_scan", "k_out_pack")
+# The paired pump runs the steps' chain (k_pack, k_dfs_pure_seed) on one stream and their backs and copies on another,
+# both FIFO: the commands are read as ONE stream, and the m-th delivery copy belongs to the m-th k_pack.
+paired = any(name == "k_dfs_pure_seed" for _s, _e, name, _st in kern)
+if paired:
+    kern = [(s, e, name, "paired") for s, e, name, st in kern]
 steps_by_stream = collections.defaultdict(list)        # stream -> list of dicts
 cur = {}
 for s, e, name, st in kern:
@@ -69,7 +77,22 @@ for lst in steps_by_stream.values():
         cand = [c for c in d2h if c[0] >= stp["k_end"] - 1000 and (nxt is None or c[0] < nxt) and c[1] - c[0] > 20000]
         if cand:
             stp["d2h"] = (cand[0][0], cand[0][1])
-delivered = [v for v in all_steps if "d2h" in v and len(v["kernels"]) >= 6]
+if paired:
+    big = [c for c in d2h if c[1] - c[0] > 20000]
+    lst = steps_by_stream["paired"]
+    # (the match is by ordinal: right when every step of the trace went through the pump's two streams.  A trace that
+    # mixes in steps on the batches' own streams — fallbacks — may deliver out of that order: the counts then differ or
+    # the spans come out negative, and the summary says so instead of reporting them)
+    n_fused = sum(1 for _s, _e, name, _st in kern if name == "k_dfs_pure_seed")
+    mismatch = len(lst) != len(big) or n_fused + 8 < len(lst)
+    if mismatch:
+        print("timeline_summary: %d k_pack, %d delivery copies, %d paired launches: steps and copies are NOT matched one "
+              "to one, the per-step spans are unreliable" % (len(lst), len(big), n_fused), file=sys.stderr)
+    for stp, c in zip(lst, big):
+        stp["d2h"] = (c[0], c[1])
+        stp["k_end"] = min(stp["k_end"], c[0])
+        stp["next_start"] = None           # (a stream's idle time between copy and k_pack has no meaning here)
+delivered = [v for v in all_steps if "d2h" in v and (paired or len(v["kernels"]) >= 6)]
 # the pipelined region: the longest stretch of delivered steps whose starts are < 2 ms apart, >= 3 streams alternating
 best, run = [], []
 for v in delivered:
@@ -81,6 +104,8 @@ for v in delivered:
 if len(run) > len(best):
     best = run
 res = {"kernel_rows": len(kern), "copy_rows": len(copies), "delivered_steps_found": len(delivered)}
+if paired:
+    res["paired_pump"] = {"steps_matched_to_copies_by_order": True, "counts_match": not mismatch}
 if len(best) >= 8:
     t0, t1 = best[0]["start"], max(v["d2h"][1] for v in best)
     wall = t1 - t0

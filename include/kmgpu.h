@@ -275,11 +275,15 @@ int km_batch_result(km_batch_t* b, km_batch_out_t* view, km_batch_sizes_t* sizes
  * interpreter between the launches.
  * Consecutive steps are PAIRED where they can be: k_seed of the next batch runs as blocks of the previous batch's
  * k_dfs_pure launch (one kernel, k_dfs_pure_seed), so that the memory-bound k_seed fills what the latency-bound walk
- * leaves idle.  Paired steps do NOT run on streams[]: the pump takes two streams of the library's pool for the call.
- * One, the chain, gets k_pack and the paired launch of every step, in order; the other, the tail, waits for an event
+ * leaves idle.  Paired steps do NOT run on streams[]: the pump takes three streams of the library's pool for the call.
+ * One, the chain, gets the paired launch of every step, in order; the second, the tail, waits for an event
  * behind each paired launch and gets the rest of the walked batch's step (large tier, k_graph, delivery kernels, the
- * copy) — so those copies follow each other on one stream.  The chain first waits for whatever the caller has put on
- * a batch's own stream; when the call returns (also with an error) no batch refers to the two streams any more.
+ * copy) — so those copies follow each other on one stream; the third, the front, gets k_pack of every next batch, and
+ * the chain waits for an event behind it (KM_PUMP_FRONT=0 in the environment: k_pack on the chain, two streams).
+ * During paired steps the callers' streams carry nothing: the front (for the first step of a run of paired steps, the
+ * chain) first waits for whatever the caller has put on a batch's own stream — a km_batch_set_targets_dev just before
+ * the call is seen by that batch's k_pack —, and when the call returns (also with an error) no batch refers to the
+ * pump's streams any more and nothing of any batch is left on them.
  * A step CAN be paired when n >= 2, both batches have targets and the next one a walkable k-mer, both databases have
  * k = 31 or neither, the previous batch's k_dfs and k_graph_pure share a launch, its walk blocks (as many as its last
  * delivery reported flagged targets, + 25 %) are all resident on the device at once, and `stages` is plain walk +

@@ -21,6 +21,8 @@ struct Knobs {
   bool fuse_pure = true;        // KM_FUSE_PURE=0: k_dfs and k_graph_pure as two launches, as before round 6 (results unchanged)
   int pair_seed = 1;            // KM_PAIR_SEED=0: km_batch_pump never runs a batch's k_seed in another batch's walk launch; 2: wherever it can, also where it does not pay (results unchanged)
   bool seed_waves = false;      // KM_SEED_WAVES=1: k_seed as single-wave blocks (k_seed_waves: what seed_body costs alone; results unchanged)
+  bool pump_front = true;       // KM_PUMP_FRONT=0: paired steps run k_pack of the next batch on the chain, in front of the paired launch, as in round 7; default: on a third stream of the pump (results unchanged)
+  bool pair_pure_last = true;   // KM_PAIR_PURE_LAST=0: the paired launch's blocks in round 7's order walk, pure-chain, seeds; default: walk, seeds, pure-chain (pair_roles.h; results unchanged)
 };
 Knobs read_knobs() {
   Knobs q;
@@ -41,6 +43,8 @@ Knobs read_knobs() {
   q.fuse_pure = num("KM_FUSE_PURE", 1) != 0;
   q.pair_seed = (int)num("KM_PAIR_SEED", 1);
   q.seed_waves = num("KM_SEED_WAVES", 0) != 0;
+  q.pump_front = num("KM_PUMP_FRONT", 1) != 0;
+  q.pair_pure_last = num("KM_PAIR_PURE_LAST", 1) != 0;
   return q;
 }
 const Knobs& knobs() {
@@ -294,8 +298,9 @@ struct Timing {
   bool timed_deliver = false;
 };
 
-struct Pairing {                   // the paired pump (result_host.h): this batch's step ran on the pump's two streams
+struct Pairing {                   // the paired pump (result_host.h): this batch's step ran on the pump's own streams
   Event ev_walked;                   // recorded behind its walk launch on the chain; the tail waits for it (made on first use)
+  Event ev_packed;                   // recorded behind its k_pack on the front; the chain waits for it (made on first use)
   bool borrowed = false;             // last_stream is one of the pump's streams (until the pump returns)
   uint32_t n_seeded = 0;             // diagnostics (km_batch_debug_counts): paired launches that seeded this batch so far
 };
@@ -936,7 +941,7 @@ struct RunFlags {
 };
 
 // ---- the step in pieces.  km_batch_run calls them in order on one stream; the paired pump (result_host.h) enqueues
-// them at different moments and on different streams: front (step_front: restore_layout, geometry, k_pack), middle
+// them at different moments and on different streams: front (step_open: restore_layout, geometry; step_pack: k_pack), middle
 // (step_seed: k_seed; step_walk: k_dfs_pure) and back (step_back: the large-tier launches, k_graph, the delivery).
 // What every run resets first.
 static void step_begin(km_batch* b, hipStream_t st, const RunFlags& f) {
@@ -1050,17 +1055,19 @@ static int step_rest(km_batch* b, hipStream_t st, const RunFlags& f) {
 }
 
 // The middle of TWO steps in one launch (graph_kernel.h: k_dfs_pure_seed): k_dfs and k_graph_pure of `prev`, whose
-// k_seed has run, and k_seed of `next`, whose k_pack is in front of this launch on `st`.  The caller has checked
-// that the two may share it (result_host.h: pairs_with).
+// k_seed has run, and k_seed of `next`, whose k_pack is in front of this launch on `st` (or `st` waits for its event).
+// The caller has checked that the two may share it (result_host.h: pairs_with).  The grid's order: walk blocks, seed
+// blocks, pure-chain blocks (pair_roles.h; KM_PAIR_PURE_LAST=0: walk, pure-chain, seeds as in round 7).
 static int launch_dfs_pure_seed(km_batch* prev, km_batch* next, hipStream_t st) {
   prev->ga.use_need_full = 1;
   const uint32_t dfs_grid = prev->hints.dfs_grid(prev->n_targets), n_pure = prev->n_targets;
   const uint64_t grid = (uint64_t)dfs_grid + n_pure + (uint64_t)(4 / SEED_WAVE_RUNS) * next->in.n_items;
   if (grid > 0x7FFFFFFFull || prev->walk_lds < SEED_WAVE_LDS) return fail(KM_E_STATE, "paired launch out of range");
+  const uint32_t pure_last = knobs().pair_pure_last ? 1u : 0u;
   if (prev->wa.tab.k == 31)
-    hipLaunchKernelGGL((k_dfs_pure_seed<31>), dim3((uint32_t)grid), dim3(64), prev->walk_lds, st, prev->wa, prev->ga, dfs_grid, n_pure, next->wa);
+    hipLaunchKernelGGL((k_dfs_pure_seed<31>), dim3((uint32_t)grid), dim3(64), prev->walk_lds, st, prev->wa, prev->ga, dfs_grid, n_pure, next->wa, pure_last);
   else
-    hipLaunchKernelGGL((k_dfs_pure_seed<0>), dim3((uint32_t)grid), dim3(64), prev->walk_lds, st, prev->wa, prev->ga, dfs_grid, n_pure, next->wa);
+    hipLaunchKernelGGL((k_dfs_pure_seed<0>), dim3((uint32_t)grid), dim3(64), prev->walk_lds, st, prev->wa, prev->ga, dfs_grid, n_pure, next->wa, pure_last);
   HIPCHK(hipGetLastError());
   return KM_OK;
 }

@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "pair_roles.h"
 #include "walk_kernel.h"
 
 namespace kmd {
@@ -301,8 +302,10 @@ void k_dfs_pure(WalkArgs wa, GraphArgs ga, uint32_t n_dfs_blocks) {
   dfs_body<false, K>(wa, blockIdx.x, n_dfs_blocks);
 }
 
-// ... and k_seed of the NEXT batch in the same launch (the paired pump, result_host.h): behind the previous batch's
-// walk blocks [0, n_dfs_blocks) and its n_pure_blocks pure-chain blocks, block n_dfs_blocks + n_pure_blocks + item runs
+// ... and k_seed of the NEXT batch in the same launch (the paired pump, result_host.h): the previous batch's walk
+// blocks [0, n_dfs_blocks), then the seed blocks of the next batch and the previous batch's n_pure_blocks pure-chain
+// blocks — seeds first by default, pure-chain blocks first as in round 7 with seeds_first = 0 (pair_roles.h: which
+// block is whose, shared with a CPU test).  Seed block `item` runs
 // seed_body (walk_kernel.h) for item record `item` of the next batch: one wave for the item's 256 seeds, four per lane
 // with their load chains in flight together (a wave of this launch has 128 vector registers and a SIMD holds four of
 // them, half of k_seed's eight: with one seed per lane the launch took as long as the two kernels one after the
@@ -313,17 +316,19 @@ void k_dfs_pure(WalkArgs wa, GraphArgs ga, uint32_t n_dfs_blocks) {
 // SEED_WAVE_LDS: its node set alone is 2 560 bytes).
 template <int K>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KM_DFS_WAVES_PER_EU)))
-void k_dfs_pure_seed(WalkArgs wa_prev, GraphArgs ga_prev, uint32_t n_dfs_blocks, uint32_t n_pure_blocks, WalkArgs wa_next) {
-  if (blockIdx.x >= n_dfs_blocks + n_pure_blocks) {
-    const uint32_t s = blockIdx.x - n_dfs_blocks - n_pure_blocks;
-    seed_body<K, false, SEED_WAVE_RUNS>(wa_next, s / (4 / SEED_WAVE_RUNS), s % (4 / SEED_WAVE_RUNS));
+void k_dfs_pure_seed(WalkArgs wa_prev, GraphArgs ga_prev, uint32_t n_dfs_blocks, uint32_t n_pure_blocks, WalkArgs wa_next,
+                     uint32_t seeds_first) {
+  const uint32_t n_seed_blocks = (4 / SEED_WAVE_RUNS) * wa_next.n_items;
+  const PairBlock r = pair_block(blockIdx.x, n_dfs_blocks, n_pure_blocks, n_seed_blocks, seeds_first);
+  if (r.role == PAIR_SEED) {
+    seed_body<K, false, SEED_WAVE_RUNS>(wa_next, r.index / (4 / SEED_WAVE_RUNS), r.index % (4 / SEED_WAVE_RUNS));
     return;
   }
-  if (blockIdx.x >= n_dfs_blocks) {
-    pure_body<K>(ga_prev, blockIdx.x - n_dfs_blocks);
+  if (r.role == PAIR_PURE) {
+    pure_body<K>(ga_prev, r.index);
     return;
   }
-  dfs_body<false, K>(wa_prev, blockIdx.x, n_dfs_blocks);
+  if (r.role == PAIR_WALK) dfs_body<false, K>(wa_prev, r.index, n_dfs_blocks);
 }
 
 // Direct mode (large tier, a.tids given): block b works on target tids[b].  LDS tier: block b

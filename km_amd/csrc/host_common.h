@@ -204,7 +204,10 @@ struct Staging {
 namespace {
 __attribute__((constructor)) void km_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
 
-constexpr int POOL_STREAMS = 7;                    // + the null stream: 8 hardware queues
+// Seven: with the null stream one per hardware queue of the library's default of 8 — and what a consumer that keeps
+// four batches in flight on four pool streams (bench.py, kmclient) leaves km_batch_pump are the three it takes for its
+// paired steps (chain, tail, front: result_host.h), so no stream is created or destroyed inside a pump call.
+constexpr int POOL_STREAMS = 7;
 struct StreamPool {
   std::vector<hipStream_t> launch;
   std::vector<char> in_use;                        // handed out by km_stream_create and not yet given back

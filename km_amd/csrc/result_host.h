@@ -142,15 +142,25 @@ extern "C" int km_batch_result(km_batch_t* b, km_batch_out_t* view, km_batch_siz
 // Consecutive steps are PAIRED where they can be: k_seed of the next batch runs as blocks of the previous batch's
 // k_dfs_pure launch (graph_kernel.h: k_dfs_pure_seed), so that the two kernels that are three quarters of a step's
 // chain — one bound by memory, one by its slowest wave — overlap whatever the streams' hardware queues do.  The
-// paired steps use TWO streams of the pump's own (pool streams held for the call), whatever n is.  The chain —
-// k_pack(next), the paired launch, k_pack, the paired launch, ... — goes to one, where each command follows the last
-// without a wait between two queues; behind every paired launch an event is recorded, and the other stream, the
+// paired steps use THREE streams of the pump's own (pool streams held for the call), whatever n is.  The chain — the
+// paired launch, the paired launch, ... — goes to one, where each launch follows the last without waiting for a
+// command that was enqueued after it; behind every paired launch an event is recorded, and the second stream, the
 // tail, waits for it and takes the back of the walked batch's step (large tier, k_graph, delivery), off the chain.
+// k_pack of the next batch needs nothing of the launch in front of it, only that the host has awaited the last
+// delivery of its workspace: it goes to the third stream, the front, with an event behind it that the chain waits for
+// before the launch that seeds that batch (KM_PUMP_FRONT=0: k_pack on the chain, in front of that launch, as in
+// round 7).  What that wins is small, 2 % of a step: in the timeline k_pack does not run beside the launch that was
+// enqueued before it, on either stream.  It starts as that launch drains, together with the tail's kernels — while
+// the launch's single-wave blocks keep the wave slots full, the blocks of another queue's kernel hardly get one —
+// and the next launch starts some 13 us after k_pack's end instead of at it.
 // (With the chain on the batches' own streams, each paired launch behind an event of the stream before it, the GPU
 // stood idle a fifth of the time; with the backs on the batches' own streams the chain shared hardware queues with
-// their copies: DESIGN.md section 5, round 7.)  The chain waits once for what the caller has put on a batch's stream
-// before the call; when the pump returns every delivery has been awaited and a batch's stream is its own again.
-// The first step of a run of paired steps seeds with the block k_seed, the last one walks with k_dfs_pure.  A step
+// their copies: DESIGN.md section 5, round 7.  The delivery copy on a fourth stream, and the front or the tail at a
+// higher stream priority, lost: round 8.)  The front waits once for what the caller has put on a batch's stream
+// before the call (the first step of a run of paired steps: the chain), and the chain gets that wait through
+// k_pack's event; when the pump returns every delivery has been awaited and a batch's stream is its own again.
+// The first step of a run of paired steps packs and seeds on the chain, with the block k_seed; the last one walks
+// with k_dfs_pure.  A step
 // that cannot be paired is km_batch_run's sequence on the batch's own stream; KM_PUMP_UNPAIRED or KM_PAIR_SEED=0:
 // every step is.
 //
@@ -216,7 +226,8 @@ extern "C" int km_batch_pump(km_batch_t* const* bs, void* const* streams, int n,
   stages &= ~(KM_PUMP_UNPAIRED | KM_PUMP_PAIRED);
   const RunFlags f(stages);
   const bool may_pair = !unpaired && pairing_allowed(n, stages) && (wherever || pairing_pays(n, f));
-  CallStream chain, tail;                // the streams of the paired steps (taken at the first such step)
+  CallStream chain, tail, front;         // the streams of the paired steps (taken at the first such step)
+  const bool use_front = knobs().pump_front;
   int chain_device = -1;                 // their device
   int cus = 0, cus_device = -1;          // the compute units of the device of the batch at hand
   auto learn_cus = [&](int device) -> int {
@@ -230,24 +241,24 @@ extern "C" int km_batch_pump(km_batch_t* const* bs, void* const* streams, int n,
   };
   km_batch* prev = nullptr;              // front and k_seed enqueued on the chain, the rest of its step not yet
   // However the call ends, no batch keeps a stream of the pump's as its last_stream: on success every delivery has
-  // been awaited; on an error return the two streams are waited for first.  (Declared behind `chain` and `tail`: it
-  // runs before they are given back.)
+  // been awaited; on an error return the pump's streams are waited for first.  (Declared behind them: it runs before
+  // they are given back.)
   struct GiveBack {
-    km_batch_t* const* bs; void* const* streams; int n; const CallStream &chain, &tail; bool ok = false;
+    km_batch_t* const* bs; void* const* streams; int n; const CallStream &chain, &tail, &front; bool ok = false;
     ~GiveBack() {
       for (int q = 0; q < n; ++q) {
         km_batch* b = bs[q];
         if (!b || !b->pair.borrowed) continue;
         if (!ok) {
           (void)hipSetDevice(b->device);
-          if (chain.st) (void)hipStreamSynchronize(chain);
-          if (tail.st) (void)hipStreamSynchronize(tail);
+          for (const CallStream* s : {&front, &chain, &tail})
+            if (s->st) (void)hipStreamSynchronize(*s);
         }
         b->last_stream = (hipStream_t)(streams ? streams[q] : nullptr);
         b->pair.borrowed = false;
       }
     }
-  } give_back{bs, streams, n, chain, tail};
+  } give_back{bs, streams, n, chain, tail, front};
   // prev's walk launch is on the chain: the tail takes the back of its step behind it
   auto back_of_prev = [&](bool fused) -> int {
     if (!prev->pair.ev_walked) HIPCHK(hipEventCreateWithFlags(&prev->pair.ev_walked.h, hipEventDisableTiming));
@@ -266,13 +277,13 @@ extern "C" int km_batch_pump(km_batch_t* const* bs, void* const* streams, int n,
     return KM_OK;
   };
   // b's step goes to the pump's streams: behind its un-awaited run of before this pump, if any, and behind what
-  // the caller has put on its stream
-  auto borrow = [&](km_batch* b, hipStream_t st, bool first_round) -> int {
+  // the caller has put on its stream (`first`: the stream of the pump that gets b's first command, its k_pack)
+  auto borrow = [&](km_batch* b, hipStream_t st, bool first_round, hipStream_t first) -> int {
     KMCHK(wait_in_flight(b));
     if (first_round) {
       if (!b->pair.ev_walked) HIPCHK(hipEventCreateWithFlags(&b->pair.ev_walked.h, hipEventDisableTiming));
       HIPCHK(hipEventRecord(b->pair.ev_walked, st));
-      HIPCHK(hipStreamWaitEvent(chain, b->pair.ev_walked, 0));
+      HIPCHK(hipStreamWaitEvent(first, b->pair.ev_walked, 0));
     }
     b->pair.borrowed = true;
     return KM_OK;
@@ -284,8 +295,20 @@ extern "C" int km_batch_pump(km_batch_t* const* bs, void* const* streams, int n,
     if (may_pair) KMCHK(learn_cus(b->device));
     if (prev && pairs(prev, b)) {
       HIPCHK(hipSetDevice(b->device));
-      KMCHK(borrow(b, st, i < n));
-      KMCHK(step_front(b, chain, f));
+      if (use_front) {
+        // k_pack(b) needs nothing of the launch in front of it on the chain, only that b's last delivery has been
+        // awaited (above): it goes to the front, and the chain waits for its event (what orders b's seeds behind
+        // whatever the caller put on b's stream, too)
+        KMCHK(borrow(b, st, i < n, front));
+        KMCHK(step_open(b, chain, f));
+        KMCHK(step_pack(b, front));
+        if (!b->pair.ev_packed) HIPCHK(hipEventCreateWithFlags(&b->pair.ev_packed.h, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(b->pair.ev_packed, front));
+        HIPCHK(hipStreamWaitEvent(chain, b->pair.ev_packed, 0));
+      } else {
+        KMCHK(borrow(b, st, i < n, chain));
+        KMCHK(step_front(b, chain, f));
+      }
       KMCHK(launch_dfs_pure_seed(prev, b, chain));
       ++b->pair.n_seeded;
       KMCHK(back_of_prev(true));
@@ -312,9 +335,10 @@ extern "C" int km_batch_pump(km_batch_t* const* bs, void* const* streams, int n,
     if (chain_device < 0) {
       KMCHK(chain.get(b->device, nullptr));
       KMCHK(tail.get(b->device, nullptr));
+      if (use_front) KMCHK(front.get(b->device, nullptr));
       chain_device = b->device;
     }
-    KMCHK(borrow(b, st, i < n));
+    KMCHK(borrow(b, st, i < n, chain));
     b->last_stream = chain;
     KMCHK(step_pack(b, chain));
     KMCHK(step_seed(b, chain));

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Summarise a rocprofv3 --kernel-trace --memory-copy-trace run of the PIPELINED bench (default: 4 batches in
 flight on 4 streams): per stream the sequence k_pack .. k_out_pack, D2H; what the copy engine and the CUs
-were doing; how long a stream sits idle between the end of its copy and its next k_pack.
+were doing; how long a stream sits idle between the end of its copy and its next k_pack.  For the paired pump
+also each of its streams by itself ("pump_streams": the queue id the trace gives it, what it carries, its busy
+time per step) and how often the paired launch started late because the k_pack it waits for had not ended.
 usage: timeline_summary.py <trace dir> <out.json>"""
 import collections
 import csv
@@ -27,17 +29,20 @@ def col(r, *names):
 
 
 kern = []
+queue_of = collections.defaultdict(set)                # stream -> the queue ids its rows carry
 for r in rows("*kernel_trace.csv"):
     name = (col(r, "Kernel_Name") or "").split("(")[0].replace("void ", "").replace("kmd::", "")
     short = name.split("<")[0]
     kern.append((int(col(r, "Start_Timestamp")), int(col(r, "End_Timestamp")), short,
                  col(r, "Stream_Id", "Queue_Id") or "?"))
+    queue_of[kern[-1][3]].add(col(r, "Queue_Id") or "?")
 copies = []
 for r in rows("*memory_copy_trace.csv"):
     copies.append((int(col(r, "Start_Timestamp")), int(col(r, "End_Timestamp")), col(r, "Direction") or "?",
                    col(r, "Stream_Id", "Queue_Id") or "?"))
 kern.sort()
 copies.sort()
+kern_by_stream = list(kern)                            # (the paired pump's kernels are read as one stream below)
 # (k_dfs_pure: k_dfs and k_graph_pure as one launch, the default since round 6 — a step then has six kernels, not seven.
 # k_dfs_pure_seed, round 7's paired pump: that launch with k_seed of the NEXT batch in it.  What a stream then shows
 # between two k_pack is k_pack of the next batch, the paired launch, and the back and the copy of the PREVIOUS batch —
@@ -150,5 +155,42 @@ if len(best) >= 8:
         "note": "kernel durations inside the pipeline are stretched by sharing the CUs with the other batches' "
                 "kernels (compare profiles/*kernel_stats.csv: each kernel alone)",
     })
+if paired and len(best) >= 8:
+    # ---- the pump's streams one by one, inside the same region
+    per_stream = collections.defaultdict(lambda: {"busy": 0, "names": collections.Counter()})
+    for s, e, name, st in kern_by_stream:
+        if name in ours and e > t0 and s < t1:
+            per_stream[("kernels", st)]["busy"] += min(e, t1) - max(s, t0)
+            per_stream[("kernels", st)]["names"][name] += 1
+    for c in d2h:
+        if c[1] > t0 and c[0] < t1 and c[1] - c[0] > 20000:
+            per_stream[("copies", c[3])]["busy"] += min(c[1], t1) - max(c[0], t0)
+            per_stream[("copies", c[3])]["names"]["delivery copy"] += 1
+    res["pump_streams"] = [
+        {"stream": st, "rows": kind, "queue_ids": sorted(queue_of.get(st, {"?"})) if kind == "kernels" else None,
+         "carries": dict(v["names"]), "busy_us_per_step": v["busy"] / 1e3 / n}
+        for (kind, st), v in sorted(per_stream.items())]
+    # ---- the chain: how long after the end of the paired launch before it does a paired launch start, and how often
+    # is the k_pack it needs still running at that end (the launch then waits for it: on the chain itself k_pack sits
+    # in that gap by construction, on the front — KM_PUMP_FRONT — only when it came late).  Every k_pack is consumed
+    # by the next k_seed or paired launch of its batch, in order: the m-th k_pack belongs to the m-th of those.
+    packs = [(s, e) for s, e, name, _st in kern_by_stream if name == "k_pack"]
+    users = [(s, e, name) for s, e, name, _st in kern_by_stream if name in ("k_seed", "k_dfs_pure_seed")]
+    matched = len(packs) == len(users)
+    gaps_all, late, after_pack, prev_end = [], [], [], None
+    for (ps, pe), (s, e, name) in zip(packs, users):
+        if name == "k_dfs_pure_seed" and prev_end is not None and s >= t0 and e <= t1:
+            gaps_all.append(s - prev_end)
+            after_pack.append(s - pe)
+            if pe > prev_end:
+                late.append(s - prev_end)
+        prev_end = e if name == "k_dfs_pure_seed" else None      # (a run of paired steps starts behind a k_seed)
+    res["chain"] = {"paired_launches_behind_a_paired_launch": len(gaps_all), "k_pack_matched_by_order": matched,
+                    "gap_between_launches_us": {"mean": sum(gaps_all) / max(1, len(gaps_all)) / 1e3,
+                                                "median": sorted(gaps_all)[len(gaps_all) // 2] / 1e3 if gaps_all else None,
+                                                "max": max(gaps_all) / 1e3 if gaps_all else None},
+                    "launch_start_after_its_k_pack_end_us": {"median": sorted(after_pack)[len(after_pack) // 2] / 1e3 if after_pack else None},
+                    "launch_waited_for_k_pack": {"count": len(late), "mean_us": sum(late) / len(late) / 1e3 if late else 0.0,
+                                                 "max_us": max(late) / 1e3 if late else 0.0}}
 json.dump(res, open(out_path, "w"), indent=1)
 print(json.dumps(res))

@@ -694,6 +694,56 @@ int kmjf_scan_text(kmjf_t* h, const uint8_t* text, const uint64_t* seq_off, uint
 /* the time of the scan kernels (extraction + lookup) of the calling thread's last call of the two above, by HIP events */
 int km_scan_kernel_ms(float* ms);
 
+/* ---- select: the FASTQ reads that hit a table, extracted on the device ---------------------- */
+/* The rule:
+ *   The input is strict 4-line FASTQ text as km_counter_add_fastq takes it, validated the same way (the same four
+ *   kinds: no '@', no '+', quality line not as long as the sequence, incomplete record).  A '\r' in front of a newline
+ *   is tolerated and is no base.
+ *   Record r is lines 4r .. 4r + 3; its bytes run from the first byte of its header to the newline of its quality
+ *   line, newlines included.
+ *   hits(r) is the number of windows of k consecutive bytes of record r's sequence line whose k bytes are all ACGTacgt
+ *   and whose k-mer has a count > 0 in the table (looked up as kmjf_cov_seqs does: the canonical form in a canonical
+ *   table).  With min_qual_char != 0 a base whose quality byte is below it is a non-base first (`count -Q`'s rule).
+ *   keep(r) = (hits(r) >= min_hits) != invert, with min_hits >= 1.
+ *   The output is the kept records in input order, byte for byte as they came in: header, '+' line, qualities and
+ *   '\r' untouched, the bases unmasked.  If the last record of a stream (final != 0) lacks its final newline and is
+ *   kept, one '\n' is written behind it, so that two streams written to one descriptor do not run together.
+ * Not covered: FASTA reads; mates kept together (kmjf_fastq_hits gives the counts for a selection of the caller's
+ * own); more than one device. */
+typedef struct km_select km_select_t;
+typedef struct { uint64_t records_in, records_out, bytes_in, bytes_out, pieces, reserved[3]; } km_select_stats_t;
+/* A selector over the uploaded table of h (which must outlive it) that writes to the descriptor out_fd.  stream: a
+ * hipStream_t for all of its work, NULL = one of the library's own.  Before any device work: KM_E_ARG for null
+ * pointers, min_hits == 0 or min_qual_char outside 0..255, KM_E_STATE without an uploaded table, KM_E_IO for a
+ * descriptor that is not open. */
+int km_select_create(kmjf_t* h, uint32_t min_hits, int invert, int min_qual_char, int out_fd, void* stream,
+                     km_select_t** out);
+/* text, n, final, *consumed as for km_counter_add_fastq: whole records are taken, the caller passes the rest again.
+ * The text crosses in pieces of whole records of at most KM_COUNT_STAGE_BYTES; the kept records of a piece are
+ * gathered on the device and only their bytes come back, while the next piece is staged and scanned; the host only
+ * calls write().  When the call returns, everything it kept has been written.  n == 0 returns KM_OK and touches
+ * nothing, except that an empty final call ends the stream: the offsets of the next one start at 0 again.
+ * KM_E_CAPACITY, naming the stream offset, when no record ends within a staging buffer.  A malformed record:
+ * KM_E_FORMAT from this very call, with the kind and the smallest offending stream offset (bytes since the last final
+ * call) in km_last_error; the piece that holds it is not written, the pieces before it are.  KM_E_IO when a write
+ * fails (EPIPE: the reader went away).  After any of these failures nothing of the call is left running on the
+ * device and every further call on the selector fails with the same code and text. */
+int km_select_add_fastq(km_select_t* s, const char* text, uint64_t n, int final, uint64_t* consumed);
+/* bytes_out counts a newline written behind a last record without one */
+int km_select_stats(km_select_t* s, km_select_stats_t* stats);
+int km_select_destroy(km_select_t* s);
+/* hits[r] = hits(r) for every record of text[0 .. n), whole records of any length (cut into pieces internally, the
+ * last line needs no newline): the first half of the selection without the gather, for callers with a rule of their
+ * own (mates of a pair, thresholds per read length).  *n_records: how many there are; KM_E_CAPACITY if more than cap.
+ * Errors as above; n == 0 returns KM_OK with *n_records = 0. */
+int kmjf_fastq_hits(kmjf_t* h, const char* text, uint64_t n, int min_qual_char, uint32_t* hits, uint64_t cap,
+                    uint64_t* n_records, void* stream);
+/* With KM_SELECT_TIME=1 in the environment of km_select_create / kmjf_fastq_hits (else no event is made and all are
+ * 0): ms[4], the kernel time by HIP events of the selector, or the kmjf_fastq_hits call, that last finished a piece on
+ * the calling thread, over all its pieces so far: [0] line table and mask, [1] clear and hits, [2] sizes and scan,
+ * [3] the gather alone */
+int km_select_kernel_ms(float* ms);
+
 /* ---- measurement helpers (bench.py at N = 1 holds no device buffers of its own) ------------- */
 int km_device_sync(int device);                                    /* hipDeviceSynchronize on `device`          */
 /* device-to-device copy of `bytes` bytes, `reps` times: read + write GB/s (the box's large-copy

@@ -1,5 +1,5 @@
 """``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, ``count``, ``merge``, ``histo``,
-``stats``, ``dump``, ``query`` and ``cov``.
+``stats``, ``dump``, ``query``, ``cov`` and ``bait``.
 
 Same flags, same ``#key:value`` echo, same TSV and ``#Elapsed time`` trailer as
 km/tools/find_mutation.py:17-60 and km/argparser/find_mutation.py:4-58, so the
@@ -463,6 +463,47 @@ def main_query(args):
         sys.exit("ERROR: query: %s" % e)
 
 
+def main_bait(args, err=None):
+    """`bait [-n N] [-v] [-Q CHAR] [-o out.fq] (-t targets.fa [-t ...] [-m K] | -d db.jf) reads.fq[.gz] ...`: the reads
+    with at least N k-mers of the bait table (with -v: the others), byte for byte and in input order, found and gathered
+    on the GPU (km_amd.count.select_files).  The table: the canonical k-mers of the FASTA records of the -t files (a
+    directory expands to its files), counted here with count_files, or an existing -d file with its own k and
+    canonical setting.  Standard output carries the records only; the figures go to standard error."""
+    err = sys.stderr if err is None else err
+    from . import count as kc
+    from . import lib
+    db = None
+    try:
+        if args.db is not None:
+            lib.jf_file_info(args.db)                     # a missing or foreign file fails before anything is opened
+            db = lib.Database.open(args.db)
+            db.upload(default_device())
+        else:
+            files = [f for t in args.targets for f in list_target_files([t])]
+            db, _ = kc.count_files(files, k=31 if args.mer_len is None else args.mer_len, canonical=True,
+                                   device=default_device())
+        n_kmers = int(db.info.n_records)
+        stats = kc.select_files(db, args.reads, out=args.output, min_hits=args.min_hits, invert=args.invert,
+                                min_qual_char=args.min_qual_char)
+    except (lib.KmError, ValueError, OSError) as e:
+        sys.exit("ERROR: bait: %s" % e)
+    finally:
+        if db is not None:
+            db.close()
+    err.write("#bait_kmers:%d\n" % n_kmers)
+    for key, name in (("records_in", "reads_in"), ("records_out", "reads_out"), ("bytes_in", "bytes_in"),
+                      ("bytes_out", "bytes_out"), ("pieces", "pieces")):
+        err.write("#%s:%d\n" % (name, stats[key]))
+
+
+def _min_hits(text):
+    """argparse type of bait's -n: a 32-bit count of at least 1."""
+    value = _count32(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError("expected at least 1, got %r" % text)
+    return value
+
+
 def _count_value(text):
     """argparse type of the count-valued options of histo / stats: a non-negative integer."""
     value = int(text)
@@ -575,6 +616,18 @@ def build_parser():
                          "the first argument that is neither a directory nor a file that starts like FASTA")
     cv.add_argument("-o", "--output", default=None, help="output file (default: standard output)")
     cv.add_argument("jellyfish_fn", nargs="*", metavar="db.jf", help="one or more databases")
+    bt = sub.add_parser("bait", help="the FASTQ reads that hit (or, with -v, miss) a k-mer table, extracted on the GPU")
+    bt.add_argument("-n", "--min-hits", type=_min_hits, default=1, metavar="N",
+                    help="keep a read with at least N k-mers of the table (default: -n 1)")
+    bt.add_argument("-v", "--invert", action="store_true", help="keep the reads that do NOT have N k-mers of the table")
+    bt.add_argument("-Q", "--min-qual-char", type=_one_char, default=None, metavar="CHAR",
+                    help="a base whose quality character is below CHAR is read as N before the k-mers are looked up")
+    bt.add_argument("-o", "--output", default=None, help="output file (default: standard output)")
+    bt.add_argument("-t", "--targets", action="append", default=[], metavar="FASTA",
+                    help="bait k-mers from the records of this FASTA file or directory; may be given several times")
+    bt.add_argument("-m", "--mer-len", type=int, default=None, help="with -t: length of the bait k-mers (default: -m 31)")
+    bt.add_argument("-d", "--db", default=None, metavar="db.jf", help="bait k-mers from an existing binary/sorted file")
+    bt.add_argument("reads", nargs="+", help="4-line FASTQ files, plain or gzip; - is stdin")
     return parser
 
 
@@ -594,7 +647,7 @@ def _looks_like_target(path):
 def parse_args(argv=None, parser=None):
     """build_parser().parse_args plus what argparse cannot say on its own, refused the same way (exit status 2):
     `dump -t` without `-c`, `query` with neither -s nor a MER, `merge` with more than one of --max / --min /
-    --subtract."""
+    --subtract, `bait` without exactly one of -t / -d or with -m beside -d."""
     parser = build_parser() if parser is None else parser
     args = parser.parse_args(argv)
     if args._cmd == "dump" and args.tab and not args.column:
@@ -603,6 +656,11 @@ def parse_args(argv=None, parser=None):
         parser.error("merge: --max, --min and --subtract exclude each other")
     if args._cmd == "query" and not args.sequence and not args.mers:
         parser.error("query: nothing to query: give -s FILE or MER arguments")
+    if args._cmd == "bait":
+        if bool(args.targets) == (args.db is not None):
+            parser.error("bait: give exactly one of -t targets.fa and -d db.jf")
+        if args.db is not None and args.mer_len is not None:
+            parser.error("bait: -m goes with -t only: a -d file has its own k")
     if args._cmd == "cov" and not args.jellyfish_fn:     # `-t a.fa b.fa db.jf ..`: -t took the databases too
         n = 0
         while n < len(args.targets) and _looks_like_target(args.targets[n]):
@@ -646,6 +704,8 @@ def main(argv=None):
         main_query(args)
     elif cmd == "cov":
         main_cov(args)
+    elif cmd == "bait":
+        main_bait(args)
     else:
         parser.print_help(sys.stderr)
         sys.exit(1)

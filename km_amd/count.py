@@ -11,7 +11,8 @@ record order (sorted on the GPU), as ``Counter.write_jf`` does for records still
 ``histo_file``, ``format_histo`` and ``format_stats`` are behind ``python -m km_amd histo`` / ``stats``: the histogram
 of a file's counts and its four statistics in one pass on the GPU.  ``dump_file`` and ``query_file`` are behind
 ``dump`` / ``query``: a file's records, or the counts of given k-mers, as text built on the GPU; the k-mers of
-``query -s`` files are cut there too.  Only the standard library and numpy.
+``query -s`` files are cut there too.  ``select_files`` is behind ``bait``: the reads of FASTQ files that hit (or
+miss) a table, found and gathered on the GPU.  Only the standard library and numpy.
 """
 
 import contextlib
@@ -90,6 +91,71 @@ def count_files(paths, k=31, canonical=True, lower_count=1, device=0, expected_d
         return db, stats, counter
     counter.close()
     return db, stats
+
+
+def _not_fastq(path):
+    return ValueError("%s does not start with '@': bait takes 4-line FASTQ reads only" % path)
+
+
+def select_files(db, paths, out=None, min_hits=1, invert=False, min_qual_char=None, block=BLOCK):
+    """The reads of the 4-line FASTQ files `paths` (plain or gzip, '-' = stdin) that hit the uploaded table `db`: a read
+    is kept iff (its windows of k bases whose k-mer `db` holds number at least min_hits) != invert, with a base whose
+    quality byte is below min_qual_char read as N first.  The kept records go to `out` (a path, a file object with
+    fileno(), or None for standard output) byte for byte and in input order, file after file; they are found and
+    gathered on the GPU (lib.Selector) and the host only writes them -> the dict of km_select_stats_t.  Every file is
+    a stream of its own, fed in blocks with the unconsumed tail carried in front of the next block and ended by a final
+    call, as feed_file does it; a last record without newline gets one.
+
+    Before `out` is opened, every file but stdin is opened once and its beginning looked at: a missing file raises
+    OSError, one whose first non-blank byte is not '@' (FASTA, for one) ValueError: reads without qualities are not
+    covered.  A malformed record raises KmError whose text names the file and the byte offset within it (of the
+    decompressed text); the pieces before it are on `out` by then, but an `out` given as a path that this call
+    created is removed again when the call fails, as for the other commands."""
+    if isinstance(paths, (str, bytes)):
+        paths = [paths]
+    paths = list(paths)
+    for path in paths:
+        if path == "-":
+            continue
+        fh, _ = _open(path)
+        try:
+            head = b""
+            while not head:
+                data = fh.read(1 << 16)
+                if not data:
+                    break
+                head = data.lstrip(b"\r\n")
+            if head and head[:1] != b"@":
+                raise _not_fastq(path)
+        finally:
+            fh.close()
+    with _text_out(out) as fd:
+        with _lib.Selector(db, fd, min_hits=min_hits, invert=invert, min_qual_char=min_qual_char) as sel:
+            for path in paths:
+                fh, close = _open(path)
+                try:
+                    tail, started = b"", False
+                    while True:
+                        data = fh.read(block)
+                        if not data:
+                            break
+                        buf = tail + data if tail else data
+                        if not started:
+                            buf = buf.lstrip(b"\r\n")
+                            if not buf:
+                                continue
+                            if buf[:1] != b"@":
+                                raise _not_fastq(path)
+                            started = True
+                        used = sel.add_fastq(buf, final=False)
+                        tail = buf[used:]
+                    sel.add_fastq(tail, final=True)          # (always: an empty one still ends the file's stream)
+                except _lib.KmError as e:
+                    raise _lib.KmError(e.code, "%s: %s" % (path, e.detail)) from e
+                finally:
+                    if close:
+                        fh.close()
+            return sel.stats()
 
 
 def merge_files(paths, mode="sum", lower_count=1, device=0, expected_distinct=0, keep_counter=False,

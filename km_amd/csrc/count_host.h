@@ -271,21 +271,46 @@ extern "C" int km_counter_add_text(km_counter_t* c, const char* text, uint64_t n
 }
 
 // ---- raw FASTQ text, parsed on the device
-static int fastq_prepare(km_counter* c) {
-  if (c->fq) return KM_OK;
-  const uint64_t stage = c->stg.bytes;
+// The buffers of the front half for pieces of at most `stage` bytes (also select_host.h's).
+static int fastq_dev_alloc(FastqDev* f, uint64_t stage) {
   if (stage >= 0xFFFFFFF0ull) return fail(KM_E_ARG, "staging buffers of %llu bytes: the line table is 32-bit",
                                           (unsigned long long)stage);
-  std::unique_ptr<FastqDev> f(new (std::nothrow) FastqDev);
-  if (!f) return fail(KM_E_NOMEM, "host allocation failed");
   const uint64_t max_tiles = (stage + FQ_TILE - 1) / FQ_TILE;
   const uint64_t max_chunks = (max_tiles + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK;
   KMCHK(f->masked.alloc(stage + COUNT_PAD));
   KMCHK(f->tiles.alloc(max_chunks * SCAN_CHUNK));
   KMCHK(f->sums.alloc(max_chunks));
-  KMCHK(f->line_start.alloc(stage + 2));              // a piece of n bytes has at most n newlines
+  KMCHK(f->line_start.alloc(stage + 2));                // a piece of n bytes has at most n newlines
+  return KM_OK;
+}
+
+static int fastq_prepare(km_counter* c) {
+  if (c->fq) return KM_OK;
+  std::unique_ptr<FastqDev> f(new (std::nothrow) FastqDev);
+  if (!f) return fail(KM_E_NOMEM, "host allocation failed");
+  KMCHK(fastq_dev_alloc(f.get(), c->stg.bytes));
   if (const char* e = getenv("KM_COUNT_TIME_FASTQ")) c->fq_spans.timed = atoi(e) != 0;
   c->fq = std::move(f);
+  return KM_OK;
+}
+
+// The front half of a FASTQ piece, d_text[0 .. n) on the device in stream order: line table -> mask into f.masked,
+// validation into error_cell.  base: the piece's offset in the stream (for what the validation reports).
+static int fastq_front(FastqDev& f, const uint8_t* d_text, uint64_t n, uint64_t base, uint32_t min_qual,
+                       unsigned long long* error_cell, hipStream_t st, uint32_t* tiles_out) {
+  const uint32_t n_tiles = (uint32_t)((n + FQ_TILE - 1) / FQ_TILE);
+  const uint32_t n_chunks = (uint32_t)(((uint64_t)n_tiles + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK);
+  HIPCHK(hipMemsetAsync(f.tiles, 0, (uint64_t)n_chunks * SCAN_CHUNK * 4, st));
+  hipLaunchKernelGGL(k_fq_count_lines, dim3(n_tiles), dim3(FQ_THREADS), 0, st, d_text, n, f.tiles.p);
+  hipLaunchKernelGGL(k_scan_reduce, dim3(n_chunks), dim3(SCAN_THREADS), 0, st, f.tiles.p, f.sums.p);
+  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, st, f.sums.p, n_chunks);
+  hipLaunchKernelGGL(k_scan_apply, dim3(n_chunks), dim3(SCAN_THREADS), 0, st, f.tiles.p, f.sums.p);
+  hipLaunchKernelGGL(k_fq_line_starts, dim3(n_tiles), dim3(FQ_THREADS), 0, st, d_text, n, f.tiles.p, n_tiles,
+                     f.line_start.p);
+  hipLaunchKernelGGL(k_fq_mask, dim3(n_tiles), dim3(FQ_THREADS), 0, st, d_text, n, f.tiles.p, n_tiles,
+                     f.line_start.p, min_qual, base, f.masked.p, error_cell);
+  HIPCHK(hipGetLastError());
+  if (tiles_out) *tiles_out = n_tiles;
   return KM_OK;
 }
 
@@ -297,19 +322,8 @@ static int fastq_enqueue(km_counter* c, const char* text, uint64_t n, uint64_t b
   memcpy(c->stg.mine, text, n);
   KMCHK(counter_reserve(c, n));                         // every byte taken as a window: a bound, and a loose one
   KMCHK(c->stg.ship(c->d_text, n, c->st));
-  const uint32_t n_tiles = (uint32_t)((n + FQ_TILE - 1) / FQ_TILE);
-  const uint32_t n_chunks = (uint32_t)(((uint64_t)n_tiles + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK);
   KMCHK(c->fq_spans.open(c->st));
-  HIPCHK(hipMemsetAsync(f.tiles, 0, (uint64_t)n_chunks * SCAN_CHUNK * 4, c->st));
-  hipLaunchKernelGGL(k_fq_count_lines, dim3(n_tiles), dim3(FQ_THREADS), 0, c->st, c->d_text.p, n, f.tiles.p);
-  hipLaunchKernelGGL(k_scan_reduce, dim3(n_chunks), dim3(SCAN_THREADS), 0, c->st, f.tiles.p, f.sums.p);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, c->st, f.sums.p, n_chunks);
-  hipLaunchKernelGGL(k_scan_apply, dim3(n_chunks), dim3(SCAN_THREADS), 0, c->st, f.tiles.p, f.sums.p);
-  hipLaunchKernelGGL(k_fq_line_starts, dim3(n_tiles), dim3(FQ_THREADS), 0, c->st, c->d_text.p, n, f.tiles.p, n_tiles,
-                     f.line_start.p);
-  hipLaunchKernelGGL(k_fq_mask, dim3(n_tiles), dim3(FQ_THREADS), 0, c->st, c->d_text.p, n, f.tiles.p, n_tiles,
-                     f.line_start.p, min_qual, base, f.masked.p, c->meta.p + CM_FORMAT);
-  HIPCHK(hipGetLastError());
+  KMCHK(fastq_front(f, c->d_text.p, n, base, min_qual, c->meta.p + CM_FORMAT, c->st, nullptr));
   KMCHK(c->fq_spans.close(c->st));
   return launch_insert(c, f.masked, n, 0);
 }

@@ -57,9 +57,7 @@ struct DumpRun {
       KMCHK(text[i].alloc(bytes_per_text + 16));
       HIPCHK(hipEventCreateWithFlags(&done[i].h, hipEventDisableTiming));
     }
-    hipError_t e = hipHostMalloc((void**)&totals.h, 16, hipHostMallocDefault);
-    if (e != hipSuccess) { totals.h = nullptr; return fail(KM_E_NOMEM, "pinned totals: %s", hipGetErrorString(e)); }
-    return KM_OK;
+    return pinned_alloc(&totals, 16, "pinned totals");
   }
   uint32_t* sums() const { return tab.p + 2ull * SCAN_CHUNK; }
   const volatile uint32_t* total_of(int buf) const { return reinterpret_cast<const uint32_t*>(totals.h) + 2 * buf; }
@@ -103,30 +101,50 @@ struct DumpRun {
   }
 };
 
-// The way out of the calls that write to a descriptor: piece after piece, formatted on `st` into the text buffer
-// whose turn it is, copied on `cs` into the pinned buffer of the same number, written to `fd` one piece later.
-struct DumpPipe {
-  DumpRun run;
+// The last leg of every call that writes device-made text to a descriptor (here and in select_host.h): per pinned
+// buffer of a Staging the bytes of the copy in flight into it; put() waits for that copy and writes them, short writes
+// and EINTR handled in dump_write_all, any other failure (EPIPE: the reader went away) is KM_E_IO.
+struct TextDrain {
   Staging* out = nullptr;
-  hipStream_t st = nullptr, cs = nullptr;
+  hipStream_t cs = nullptr;               // the copy stream
   int fd = -1;
-  km_dump_stats_t stats;
   uint64_t pending[2] = {0, 0};           // bytes of the copy in flight into out->pin[i]
+  bool close_line[2] = {false, false};    // the text in out->pin[i] gets a newline behind it unless it ends in one
+  uint64_t closed = 0;                    // (the buffers have a byte of padding for it) ... and how often that happened
+  // bytes of d_src (ready: the host has waited for what wrote them) on their way into out->pin[buf]
+  int fetch(int buf, const void* d_src, uint64_t bytes) {
+    if (bytes) KMCHK(out->fetch(buf, d_src, bytes, cs));
+    pending[buf] = bytes;
+    return KM_OK;
+  }
+  int put(int buf) {                      // the text copied into out->pin[buf] goes to fd
+    if (!pending[buf]) return KM_OK;
+    unsigned char* got = nullptr;
+    KMCHK(out->wait(buf, &got));
+    uint64_t n = pending[buf];
+    pending[buf] = 0;
+    if (close_line[buf] && got[n - 1] != '\n') {
+      got[n++] = '\n';
+      ++closed;
+    }
+    close_line[buf] = false;
+    if (const int e = dump_write_all(fd, got, n)) return fail(KM_E_IO, "writing the text failed: %s", strerror(e));
+    return KM_OK;
+  }
+};
+
+// The way out of the calls that write records as text: piece after piece, formatted on `st` into the text buffer
+// whose turn it is, copied on `cs` into the pinned buffer of the same number, written to `fd` one piece later.
+struct DumpPipe : TextDrain {
+  DumpRun run;
+  hipStream_t st = nullptr;
+  km_dump_stats_t stats;
   int turn = 0;
   DumpPipe() { memset(&stats, 0, sizeof stats); }
   // never leaves a copy into a freed buffer, or a kernel on a freed table, in flight
   ~DumpPipe() {
     if (st) (void)hipStreamSynchronize(st);
     if (cs) (void)hipStreamSynchronize(cs);
-  }
-  int put(int buf) {                      // the text copied into out->pin[buf] goes to fd
-    if (!pending[buf]) return KM_OK;
-    unsigned char* got = nullptr;
-    KMCHK(out->wait(buf, &got));
-    const uint64_t n = pending[buf];
-    pending[buf] = 0;
-    if (const int e = dump_write_all(fd, got, n)) return fail(KM_E_IO, "writing the text failed: %s", strerror(e));
-    return KM_OK;
   }
   template <typename Src>
   int piece(const Src& src, uint64_t n) {
@@ -140,9 +158,7 @@ struct DumpPipe {
     stats.records_out += kept;
     stats.bytes_out += bytes;
     ++stats.pieces;
-    if (bytes) KMCHK(out->fetch(buf, run.text[buf].p, bytes, cs));
-    pending[buf] = bytes;
-    return KM_OK;
+    return fetch(buf, run.text[buf].p, bytes);
   }
   int finish(km_dump_stats_t* to) {
     KMCHK(put(turn));                     // (the older of the two first)

@@ -112,6 +112,13 @@ using File = Owned<FILE*, fclose>;
 struct Unmap { size_t len; void operator()(void* p) const { munmap(p, len); } };
 using Mapping = std::unique_ptr<void, Unmap>;
 
+// bytes of pinned host memory into an (empty) owner
+static int pinned_alloc(Pinned* to, uint64_t bytes, const char* what) {
+  hipError_t e = hipHostMalloc((void**)&to->h, bytes, hipHostMallocDefault);
+  if (e != hipSuccess) { to->h = nullptr; return fail(KM_E_NOMEM, "%s: %s", what, hipGetErrorString(e)); }
+  return KM_OK;
+}
+
 // Timing of kernels that an environment variable asks for: an event pair around each run of them on one stream.
 // Does nothing unless `timed`.  The owner declares it after its stream: the events go before the stream.
 struct KernelSpans {
@@ -161,8 +168,7 @@ struct Staging {
   Staging() { if (const char* e = getenv("KM_COUNT_STAGE_BYTES")) bytes = std::max<uint64_t>(256, strtoull(e, nullptr, 10)); }
   int alloc(uint64_t pad) {               // the buffers, of bytes + pad each, and their events
     for (int i = 0; i < 2; ++i) {
-      hipError_t e = hipHostMalloc((void**)&pin[i].h, bytes + pad, hipHostMallocDefault);
-      if (e != hipSuccess) { pin[i].h = nullptr; return fail(KM_E_NOMEM, "pinned staging buffer: %s", hipGetErrorString(e)); }
+      KMCHK(pinned_alloc(&pin[i], bytes + pad, "pinned staging buffer"));
       HIPCHK(hipEventCreateWithFlags(&copied[i].h, hipEventDisableTiming));
     }
     return KM_OK;

@@ -23,6 +23,8 @@
 //                  formatted on the device piece by piece and written to a descriptor (a Staging in, a Staging out)
 //   scan_host.h    kmjf_cov_seqs, kmjf_scan_text: the k-mers of sequences cut and looked up on the device, as per-sequence
 //                  coverage statistics or as the text of `query` (a Staging in; the text through dump_host.h's DumpPipe)
+//   select_host.h  km_select_*, kmjf_fastq_hits: the FASTQ records that hit the table, found and gathered on the device
+//                  (count_host.h's front half of a FASTQ piece, a Staging in, the kept bytes out through TextDrain)
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
 #include <hip/hip_runtime.h>
@@ -66,6 +68,8 @@
 #include "setops_kernel.h"      // (after those above: the kernels before it keep their places in the code object)
 #include "scan_kernel.h"
 #include "scan_rule.h"
+#include "select_kernel.h"
+#include "select_rule.h"
 
 using namespace kmd;
 
@@ -82,3 +86,4 @@ using namespace kmd;
 #include "histo_host.h"
 #include "dump_host.h"
 #include "scan_host.h"
+#include "select_host.h"

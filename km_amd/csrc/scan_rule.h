@@ -59,8 +59,10 @@ KM_SCAN_HD inline bool window_in_seq(uint64_t start, int k, uint64_t seq_begin, 
 }
 
 // The sequence of byte `pos`: the last q of [lo, hi] with off[q] <= pos (the caller knows off[lo] <= pos).  Empty
-// sequences in front of pos are passed over: they own no byte.
-KM_SCAN_HD inline uint64_t seq_of(const uint64_t* off, uint64_t lo, uint64_t hi, uint64_t pos) {
+// sequences in front of pos are passed over: they own no byte.  (Off: uint64_t offsets of a call's text, or the 32-bit
+// line starts of a FASTQ piece, select_rule.h)
+template <typename Off>
+KM_SCAN_HD inline uint64_t seq_of(const Off* off, uint64_t lo, uint64_t hi, uint64_t pos) {
   while (lo < hi) {
     const uint64_t mid = lo + (hi - lo + 1) / 2;
     if (off[mid] <= pos) lo = mid;
@@ -116,9 +118,9 @@ KM_SCAN_HD inline void acc_count(Acc& a, uint32_t c) {
 //   sink.window(j, fwd, rev, valid)        the window that starts at g0 + j (j < own) lies in the current sequence;
 //                                          fwd / rev: its key and the reverse complement's when valid
 // Returns the sequence the lane ended in.
-template <typename Sink>
+template <typename Sink, typename Off>
 KM_SCAN_HD inline uint64_t lane_walk(const uint32_t (&w)[16], uint64_t g0, uint32_t own, uint64_t end_all,
-                                     const uint64_t* off, uint64_t q, int k, Sink& sink) {
+                                     const Off* off, uint64_t q, int k, Sink& sink) {
   const uint64_t kmask = k >= 32 ? ~0ull : ((1ull << (2 * k)) - 1);
   const uint32_t rshift = 2u * (uint32_t)(k - 1);
   const uint32_t jend = (uint32_t)k + own - 1;               // bytes this lane looks at (<= 63)

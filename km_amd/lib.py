@@ -47,6 +47,8 @@ SYMBOLS = [
     "km_histo_layout", "km_counter_histo", "km_jf_histo", "km_histo_kernel_ms", "km_histo_text", "km_histo_stats_text",
     "km_dump_text", "km_jf_dump", "km_counter_dump", "kmjf_query_text", "km_dump_kernel_ms",
     "kmjf_cov_seqs", "kmjf_scan_text", "km_scan_kernel_ms",
+    "km_select_create", "km_select_add_fastq", "km_select_stats", "km_select_destroy", "kmjf_fastq_hits",
+    "km_select_kernel_ms",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
 ]
 
@@ -54,6 +56,7 @@ SYMBOLS = [
 class KmError(RuntimeError):
     def __init__(self, code, detail):
         self.code = code
+        self.detail = detail
         super().__init__("libkmgpu: %s" % detail)
 
 
@@ -92,6 +95,12 @@ class DumpStats(C.Structure):
     """km_dump_stats_t (include/kmgpu.h)."""
     _fields_ = [("records_in", C.c_uint64), ("records_out", C.c_uint64), ("bytes_out", C.c_uint64),
                 ("pieces", C.c_uint64), ("reserved", C.c_uint64 * 4)]
+
+
+class SelectStats(C.Structure):
+    """km_select_stats_t (include/kmgpu.h)."""
+    _fields_ = [("records_in", C.c_uint64), ("records_out", C.c_uint64), ("bytes_in", C.c_uint64),
+                ("bytes_out", C.c_uint64), ("pieces", C.c_uint64), ("reserved", C.c_uint64 * 3)]
 
 
 class TextState(C.Structure):
@@ -285,6 +294,12 @@ def load():
         "kmjf_cov_seqs": [vp, vp, vp, u64, vp, vp],
         "kmjf_scan_text": [vp, vp, vp, u64, i32, C.POINTER(DumpStats), vp],
         "km_scan_kernel_ms": [C.POINTER(C.c_float)],
+        "km_select_create": [vp, u32, i32, i32, i32, vp, C.POINTER(vp)],
+        "km_select_add_fastq": [vp, vp, u64, i32, C.POINTER(u64)],
+        "km_select_stats": [vp, C.POINTER(SelectStats)],
+        "km_select_destroy": [vp],
+        "kmjf_fastq_hits": [vp, vp, u64, i32, vp, u64, C.POINTER(u64), vp],
+        "km_select_kernel_ms": [C.POINTER(C.c_float)],
         "km_device_count": [C.POINTER(i32)],
         "km_device_sync": [i32],
         "km_device_copy_GBs": [i32, u64, i32, C.POINTER(dbl)],
@@ -511,6 +526,19 @@ class Database:
         check(self._lib.kmjf_scan_text(self._h, ptr(text) if text.size else None, ptr(off), off.size - 1,
                                        out_descriptor(out_fd), C.byref(st), C.c_void_p(stream or 0)))
         return _dump_stats_dict(st)
+
+    def fastq_hits(self, text, min_qual_char=None, stream=None):
+        """kmjf_fastq_hits: per record of the 4-line FASTQ text (whole records, the last line needs no newline) the
+        number of windows of k bases of its sequence line whose k-mer this table holds with a count > 0; with
+        min_qual_char a base whose quality byte is below it is no base -> np.uint32[n_records].  Cut, masked and looked
+        up on the device; a malformed record raises KmError (KM_E_FORMAT)."""
+        buf = _byte_view(text)
+        hits = np.zeros(buf.size // 6 + 1, np.uint32)          # the smallest record has six bytes
+        n = C.c_uint64()
+        check(self._lib.kmjf_fastq_hits(self._h, ptr(buf) if buf.size else None, buf.size,
+                                        _qual_byte(min_qual_char or 0), ptr(hits), hits.size, C.byref(n),
+                                        C.c_void_p(stream or 0)))
+        return hits[:n.value].copy()
 
 
 def _byte_view(data):
@@ -830,6 +858,62 @@ def scan_kernel_ms():
     ms = C.c_float()
     check(load().km_scan_kernel_ms(C.byref(ms)))
     return float(ms.value)
+
+
+class Selector:
+    """The FASTQ reads that hit a table, extracted on the GPU (km_select_*, include/kmgpu.h): a read is kept iff
+    (its windows of k bases with a count > 0 in `db` number at least min_hits) != invert, and the kept records go to
+    `out` (a descriptor, or a file object with fileno()) byte for byte, in input order.  `db` must stay open for as long
+    as the selector lives.  A context manager; close() releases the device side."""
+
+    def __init__(self, db, out, min_hits=1, invert=False, min_qual_char=None, stream=None):
+        self._lib = load()
+        self._s = C.c_void_p()
+        self._db = db
+        check(self._lib.km_select_create(db._h, int(min_hits), int(bool(invert)), _qual_byte(min_qual_char or 0),
+                                         out_descriptor(out), C.c_void_p(stream or 0), C.byref(self._s)))
+        _LIVE_COUNTERS.add(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._s is not None and self._s.value:
+            self._lib.km_select_destroy(self._s)
+        self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_fastq(self, data, final=False):
+        """4-line FASTQ text; returns how many bytes were taken (whole records): pass the rest again in front of the
+        next block.  What the call kept is on the descriptor when it returns.  A malformed record raises KmError
+        (KM_E_FORMAT) from this call; the pieces before it are written."""
+        buf = _byte_view(data)
+        consumed = C.c_uint64()
+        check(self._lib.km_select_add_fastq(self._s, ptr(buf) if buf.size else None, buf.size, int(bool(final)),
+                                            C.byref(consumed)))
+        return int(consumed.value)
+
+    def stats(self):
+        st = SelectStats()
+        check(self._lib.km_select_stats(self._s, C.byref(st)))
+        return {name: int(getattr(st, name)) for name in ("records_in", "records_out", "bytes_in", "bytes_out", "pieces")}
+
+
+def select_kernel_ms():
+    """km_select_kernel_ms (needs KM_SELECT_TIME=1 when the selector is made, else zeros): the kernel time of the
+    Selector, or the Database.fastq_hits call, that last finished a piece on this thread -> {"front": line table and
+    mask, "hits": clear and hits, "sizes": sizes and scan, "gather": the gather alone}, ms."""
+    ms = (C.c_float * 4)()
+    check(load().km_select_kernel_ms(ms))
+    return {"front": float(ms[0]), "hits": float(ms[1]), "sizes": float(ms[2]), "gather": float(ms[3])}
 
 
 MERGE_MODES = {"sum": 0, "max": 1}         # KM_MERGE_SUM, KM_MERGE_MAX

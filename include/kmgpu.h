@@ -708,8 +708,7 @@ int km_scan_kernel_ms(float* ms);
  *   The output is the kept records in input order, byte for byte as they came in: header, '+' line, qualities and
  *   '\r' untouched, the bases unmasked.  If the last record of a stream (final != 0) lacks its final newline and is
  *   kept, one '\n' is written behind it, so that two streams written to one descriptor do not run together.
- * Not covered: FASTA reads; mates kept together (kmjf_fastq_hits gives the counts for a selection of the caller's
- * own); more than one device. */
+ * Not covered: FASTA reads; more than one device.  (Mates of a pair kept together: km_select_pair_* below.) */
 typedef struct km_select km_select_t;
 typedef struct { uint64_t records_in, records_out, bytes_in, bytes_out, pieces, reserved[3]; } km_select_stats_t;
 /* A selector over the uploaded table of h (which must outlive it) that writes to the descriptor out_fd.  stream: a
@@ -743,6 +742,59 @@ int kmjf_fastq_hits(kmjf_t* h, const char* text, uint64_t n, int min_qual_char, 
  * the calling thread, over all its pieces so far: [0] line table and mask, [1] clear and hits, [2] sizes and scan,
  * [3] the gather alone */
 int km_select_kernel_ms(float* ms);
+
+/* ---- select, pairs: the mates of a paired-end run kept together ----------------------------- */
+/* The rule (this project's own definition: the reference has no paired selection to compare with):
+ *   Two FASTQ streams, mate 1 and mate 2, whose records correspond one to one: record r of either is pair r.  Each
+ *   stream is taken and validated as km_select_add_fastq takes one.
+ *   h1(r), h2(r) are hits(r) of record r of mate 1 and of mate 2 exactly as defined above; the same table, k, canonical
+ *   setting and quality masking apply to both mates.
+ *   score(r) depends on the pair rule:
+ *     KM_PAIR_ANY  (0, the default of the callers): max(h1, h2)
+ *     KM_PAIR_BOTH (1): min(h1, h2)
+ *     KM_PAIR_SUM  (2): h1 + h2, saturating at 2^32 - 1
+ *   keep(r) = (score(r) >= min_hits) != invert.  A pair is kept or dropped whole; invert inverts the pair's decision.
+ *   Mate 1's kept records go to one descriptor and mate 2's to another, both byte for byte and in input order, so record
+ *   i of one output is the mate of record i of the other.
+ *   The name check (on unless check_names == 0): the name of a record is the bytes of its header line behind '@', up to
+ *   but not including the first space, tab, '\r' or '\n'.  If that name is at least two bytes long and ends in "/1" or
+ *   "/2", those two bytes are dropped.  Mates agree iff their names are byte-equal.  The first pair that disagrees is a
+ *   format error that names the pair's index within the stream (from 0, over all calls since the last final one) and the
+ *   byte offsets of both headers within their streams.  With the check off, names are not looked at.
+ *   When the final call arrives and one stream still holds a record while the other has none, that is a format error
+ *   ("mate files differ in their number of records") that names the mate with more and the index of the first pair
+ *   without a partner.
+ *   A malformed record in either mate is reported as by km_select_add_fastq, with "mate 1" or "mate 2" in front.
+ *   After any error, the whole pieces before the failing one are on both descriptors and the failing piece leaves nothing
+ *   on either: each output is a prefix of what a fault-free run would write, and both prefixes end at the same pair.  The
+ *   selector is dead afterwards, as a km_select_t is.  Where a stream holds several faults, which one is reported is
+ *   not specified.
+ *   A kept last record without a final newline gets one, decided in each output independently.
+ * Not covered: interleaved input or output, orphan files for half-matching pairs, FASTA reads, more than one device. */
+enum { KM_PAIR_ANY = 0, KM_PAIR_BOTH = 1, KM_PAIR_SUM = 2 };
+typedef struct km_select_pair km_select_pair_t;
+/* bytes_in: consumed, not counting bytes sent again; resent_bytes: the bytes of whole records that went to the device in
+ * a piece, found no partner there and went again at the head of the next piece */
+typedef struct {
+  uint64_t pairs_in, pairs_out, bytes_in[2], bytes_out[2], pieces, resent_bytes[2], reserved[3];
+} km_select_pair_stats_t;
+/* As km_select_create, with the pair rule, the name check and a descriptor per mate.  KM_E_ARG in addition for an
+ * unknown rule and for out_fd1 == out_fd2. */
+int km_select_pair_create(kmjf_t* h, uint32_t min_hits, int invert, int min_qual_char, int rule, int check_names,
+                          int out_fd1, int out_fd2, void* stream, km_select_pair_t** out);
+/* text1/n1 and text2/n2 as text/n of km_select_add_fastq, one per mate; *consumed1, *consumed2 follow its protocol:
+ * the caller passes the rest of either stream again in front of its next block.  A piece is one staging buffer's worth
+ * of whole records from each stream; the device pairs the first R = min(records of the two) of them, the host advances
+ * each stream by what those took, and the longer side's surplus records go to the device again with the next piece.
+ * A non-final call in which either side holds no whole record consumes nothing of either and succeeds.  A final call
+ * ends both streams: offsets and pair indices of the next ones start at 0.  Errors as above and as for
+ * km_select_add_fastq. */
+int km_select_pair_add_fastq(km_select_pair_t* s, const char* text1, uint64_t n1, const char* text2, uint64_t n2, int final,
+                             uint64_t* consumed1, uint64_t* consumed2);
+/* bytes_out counts a newline written behind a last record without one.  KM_SELECT_TIME=1 fills km_select_kernel_ms for a
+ * pair selector too, both mates summed: [2] holds the pair's sizes, the name check and the scans, [3] the one gather. */
+int km_select_pair_stats(km_select_pair_t* s, km_select_pair_stats_t* stats);
+int km_select_pair_destroy(km_select_pair_t* s);
 
 /* ---- measurement helpers (bench.py at N = 1 holds no device buffers of its own) ------------- */
 int km_device_sync(int device);                                    /* hipDeviceSynchronize on `device`          */

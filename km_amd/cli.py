@@ -468,7 +468,12 @@ def main_bait(args, err=None):
     with at least N k-mers of the bait table (with -v: the others), byte for byte and in input order, found and gathered
     on the GPU (km_amd.count.select_files).  The table: the canonical k-mers of the FASTA records of the -t files (a
     directory expands to its files), counted here with count_files, or an existing -d file with its own k and
-    canonical setting.  Standard output carries the records only; the figures go to standard error."""
+    canonical setting.  Standard output carries the records only; the figures go to standard error.
+
+    Paired-end: `bait ... -1 R1.fq[.gz] [-1 ...] -2 R2.fq[.gz] [-2 ...] -o out_1.fq -O out_2.fq [--pair-rule any|both|sum]
+    [--no-name-check]` keeps or drops the mates of a pair together (km_amd.count.select_pair_files), so the two outputs
+    line up record for record; the figures are then #pairs_in, #pairs_out, #bytes_in_1/2, #bytes_out_1/2, #pieces and
+    #pair_rule."""
     err = sys.stderr if err is None else err
     from . import count as kc
     from . import lib
@@ -483,14 +488,26 @@ def main_bait(args, err=None):
             db, _ = kc.count_files(files, k=31 if args.mer_len is None else args.mer_len, canonical=True,
                                    device=default_device())
         n_kmers = int(db.info.n_records)
-        stats = kc.select_files(db, args.reads, out=args.output, min_hits=args.min_hits, invert=args.invert,
-                                min_qual_char=args.min_qual_char)
+        if args.mate1:
+            stats = kc.select_pair_files(db, args.mate1, args.mate2, args.output, args.output2, min_hits=args.min_hits,
+                                         invert=args.invert, min_qual_char=args.min_qual_char,
+                                         rule=args.pair_rule or "any", check_names=not args.no_name_check)
+        else:
+            stats = kc.select_files(db, args.reads, out=args.output, min_hits=args.min_hits, invert=args.invert,
+                                    min_qual_char=args.min_qual_char)
     except (lib.KmError, ValueError, OSError) as e:
         sys.exit("ERROR: bait: %s" % e)
     finally:
         if db is not None:
             db.close()
     err.write("#bait_kmers:%d\n" % n_kmers)
+    if args.mate1:
+        err.write("#pairs_in:%d\n#pairs_out:%d\n" % (stats["pairs_in"], stats["pairs_out"]))
+        for key in ("bytes_in", "bytes_out"):
+            for mate in (0, 1):
+                err.write("#%s_%d:%d\n" % (key, mate + 1, stats[key][mate]))
+        err.write("#pieces:%d\n#pair_rule:%s\n" % (stats["pieces"], args.pair_rule or "any"))
+        return
     for key, name in (("records_in", "reads_in"), ("records_out", "reads_out"), ("bytes_in", "bytes_in"),
                       ("bytes_out", "bytes_out"), ("pieces", "pieces")):
         err.write("#%s:%d\n" % (name, stats[key]))
@@ -627,7 +644,16 @@ def build_parser():
                     help="bait k-mers from the records of this FASTA file or directory; may be given several times")
     bt.add_argument("-m", "--mer-len", type=int, default=None, help="with -t: length of the bait k-mers (default: -m 31)")
     bt.add_argument("-d", "--db", default=None, metavar="db.jf", help="bait k-mers from an existing binary/sorted file")
-    bt.add_argument("reads", nargs="+", help="4-line FASTQ files, plain or gzip; - is stdin")
+    bt.add_argument("-1", "--mate1", action="append", default=[], metavar="R1.fq",
+                    help="paired-end: a mate-1 file; the i-th -1 pairs with the i-th -2, and a pair is kept or dropped whole")
+    bt.add_argument("-2", "--mate2", action="append", default=[], metavar="R2.fq", help="paired-end: the mate-2 file of a -1")
+    bt.add_argument("-O", "--output2", default=None, metavar="out_2.fq",
+                    help="with -1/-2: the kept mate-2 records (-o takes the mate-1 records)")
+    bt.add_argument("--pair-rule", choices=("any", "both", "sum"), default=None,
+                    help="with -1/-2: N k-mers in either mate (any, the default), in each mate (both) or in the two together (sum)")
+    bt.add_argument("--no-name-check", action="store_true",
+                    help="with -1/-2: do not compare the mates' names (a /1 or /2 at the end is ignored by the check)")
+    bt.add_argument("reads", nargs="*", help="4-line FASTQ files, plain or gzip; - is stdin")
     return parser
 
 
@@ -647,7 +673,9 @@ def _looks_like_target(path):
 def parse_args(argv=None, parser=None):
     """build_parser().parse_args plus what argparse cannot say on its own, refused the same way (exit status 2):
     `dump -t` without `-c`, `query` with neither -s nor a MER, `merge` with more than one of --max / --min /
-    --subtract, `bait` without exactly one of -t / -d or with -m beside -d."""
+    --subtract, `bait` without exactly one of -t / -d or with -m beside -d, without reads, with unequal numbers of -1 and
+    -2, with plain reads beside them, with -1/-2 but not both of -o and -O or with one path for both, and with -O,
+    --pair-rule or --no-name-check but no -1/-2."""
     parser = build_parser() if parser is None else parser
     args = parser.parse_args(argv)
     if args._cmd == "dump" and args.tab and not args.column:
@@ -661,6 +689,20 @@ def parse_args(argv=None, parser=None):
             parser.error("bait: give exactly one of -t targets.fa and -d db.jf")
         if args.db is not None and args.mer_len is not None:
             parser.error("bait: -m goes with -t only: a -d file has its own k")
+        if args.mate1 or args.mate2:
+            if len(args.mate1) != len(args.mate2):
+                parser.error("bait: every -1 file needs its -2 file: %d of -1, %d of -2" % (len(args.mate1), len(args.mate2)))
+            if args.reads:
+                parser.error("bait: give the reads either as -1/-2 pairs or as plain arguments, not both")
+            if args.output is None or args.output2 is None:
+                parser.error("bait: -1/-2 need both -o and -O: standard output cannot carry two files")
+            if os.path.abspath(args.output) == os.path.abspath(args.output2):
+                parser.error("bait: -o and -O name one file")
+        else:
+            if not args.reads:
+                parser.error("bait: no reads: give FASTQ files, or -1/-2 pairs")
+            if args.output2 is not None or args.pair_rule is not None or args.no_name_check:
+                parser.error("bait: -O, --pair-rule and --no-name-check go with -1/-2 only")
     if args._cmd == "cov" and not args.jellyfish_fn:     # `-t a.fa b.fa db.jf ..`: -t took the databases too
         n = 0
         while n < len(args.targets) and _looks_like_target(args.targets[n]):

@@ -97,6 +97,124 @@ def _not_fastq(path):
     return ValueError("%s does not start with '@': bait takes 4-line FASTQ reads only" % path)
 
 
+def _preflight(paths):
+    """Every file but stdin is opened once and its beginning looked at: OSError for a missing one, ValueError for one
+    whose first non-blank byte is not '@'."""
+    for path in paths:
+        if path == "-":
+            continue
+        fh, _ = _open(path)
+        try:
+            head = b""
+            while not head:
+                data = fh.read(1 << 16)
+                if not data:
+                    break
+                head = data.lstrip(b"\r\n")
+            if head and head[:1] != b"@":
+                raise _not_fastq(path)
+        finally:
+            fh.close()
+
+
+class _Blocks:
+    """One FASTQ file as the blocks a selector takes: next() -> the unconsumed tail with the next block of the file
+    behind it (leading blank lines dropped), used(n) says how much of it was taken; done: the file has been read to
+    its end, so what next() returns is all there will be."""
+
+    def __init__(self, path, block):
+        self.path, self.block = path, block
+        self.fh, self.close_it = _open(path)
+        self.tail, self.started, self.done = b"", False, False
+
+    def next(self):
+        while not self.done:
+            data = self.fh.read(self.block)
+            if not data:
+                self.done = True
+                break
+            buf = self.tail + data if self.tail else data
+            if not self.started:
+                buf = buf.lstrip(b"\r\n")
+                if not buf:
+                    continue
+                if buf[:1] != b"@":
+                    raise _not_fastq(self.path)
+                self.started = True
+            self.tail = buf
+            break
+        return self.tail
+
+    def used(self, n):
+        self.tail = self.tail[n:]
+
+    def close(self):
+        if self.close_it:
+            self.fh.close()
+
+
+def select_pair_files(db, paths1, paths2, out1, out2, min_hits=1, invert=False, min_qual_char=None, rule="any",
+                      check_names=True, block=BLOCK):
+    """select_files for the two mate files of paired-end runs: file i of `paths1` pairs with file i of `paths2`, record
+    r of one with record r of the other, and a pair is kept or dropped whole (lib.PairSelector: rule "any", "both" or
+    "sum"; check_names compares the mates' names).  Mate 1's kept records go to `out1` and mate 2's to `out2` (paths or
+    file objects with fileno()), byte for byte and in input order, so the outputs line up record for record -> the dict
+    of km_select_pair_stats_t.  Files are plain or gzip; at most one may be '-' (stdin).  Each file pair is a pair of
+    streams of its own, fed in blocks with either unconsumed tail carried in front of that file's next block, and ended
+    by a final call.
+
+    The lists must have equal length (ValueError).  Before either output is opened, the pre-flight checks of
+    select_files run for all files of both lists.  A KmError names both files of the pair.  An output given as a path
+    that this call created is removed again when the call fails; that holds for both outputs."""
+    if isinstance(paths1, (str, bytes)):
+        paths1 = [paths1]
+    if isinstance(paths2, (str, bytes)):
+        paths2 = [paths2]
+    paths1, paths2 = list(paths1), list(paths2)
+    if len(paths1) != len(paths2):
+        raise ValueError("%d mate-1 files but %d mate-2 files: every file needs its mate file" % (len(paths1), len(paths2)))
+    if not paths1:
+        raise ValueError("no input files")
+    if (paths1 + paths2).count("-") > 1:
+        raise ValueError("at most one input may be '-': standard input can be read once")
+    if out1 is None or out2 is None:
+        raise ValueError("paired output needs two outputs: standard output cannot carry two files")
+    same = out1 is out2
+    if not same and all(isinstance(o, (str, bytes, os.PathLike)) for o in (out1, out2)):
+        same = os.path.abspath(os.fspath(out1)) == os.path.abspath(os.fspath(out2))
+    if same:
+        raise ValueError("the two outputs are one: mate 1 and mate 2 need a file each")
+    _preflight(paths1 + paths2)
+    with _text_out(out1) as fd1, _text_out(out2) as fd2:
+        with _lib.PairSelector(db, fd1, fd2, min_hits=min_hits, invert=invert, min_qual_char=min_qual_char, rule=rule,
+                               check_names=check_names) as sel:
+            for path1, path2 in zip(paths1, paths2):
+                mates = []
+                try:
+                    mates.append(_Blocks(path1, block))
+                    mates.append(_Blocks(path2, block))
+                    a, b = mates
+                    while True:
+                        # read where the selector ran dry; a side that is far ahead waits with what it holds
+                        need_a = not a.done and (len(a.tail) <= len(b.tail) or b.done)
+                        need_b = not b.done and (len(b.tail) <= len(a.tail) or a.done)
+                        buf1 = a.next() if need_a else a.tail
+                        buf2 = b.next() if need_b else b.tail
+                        if a.done and b.done:
+                            break
+                        used1, used2 = sel.add_fastq(buf1, buf2, final=False)
+                        del buf1, buf2                            # (freed before the next two blocks are read)
+                        a.used(used1)
+                        b.used(used2)
+                    sel.add_fastq(a.tail, b.tail, final=True)     # (always: an empty one still ends the pair of streams)
+                except _lib.KmError as e:
+                    raise _lib.KmError(e.code, "%s, %s: %s" % (path1, path2, e.detail)) from e
+                finally:
+                    for m in mates:
+                        m.close()
+            return sel.stats()
+
+
 def select_files(db, paths, out=None, min_hits=1, invert=False, min_qual_char=None, block=BLOCK):
     """The reads of the 4-line FASTQ files `paths` (plain or gzip, '-' = stdin) that hit the uploaded table `db`: a read
     is kept iff (its windows of k bases whose k-mer `db` holds number at least min_hits) != invert, with a base whose
@@ -114,21 +232,7 @@ def select_files(db, paths, out=None, min_hits=1, invert=False, min_qual_char=No
     if isinstance(paths, (str, bytes)):
         paths = [paths]
     paths = list(paths)
-    for path in paths:
-        if path == "-":
-            continue
-        fh, _ = _open(path)
-        try:
-            head = b""
-            while not head:
-                data = fh.read(1 << 16)
-                if not data:
-                    break
-                head = data.lstrip(b"\r\n")
-            if head and head[:1] != b"@":
-                raise _not_fastq(path)
-        finally:
-            fh.close()
+    _preflight(paths)
     with _text_out(out) as fd:
         with _lib.Selector(db, fd, min_hits=min_hits, invert=invert, min_qual_char=min_qual_char) as sel:
             for path in paths:

@@ -25,6 +25,8 @@
 //                  coverage statistics or as the text of `query` (a Staging in; the text through dump_host.h's DumpPipe)
 //   select_host.h  km_select_*, kmjf_fastq_hits: the FASTQ records that hit the table, found and gathered on the device
 //                  (count_host.h's front half of a FASTQ piece, a Staging in, the kept bytes out through TextDrain)
+//   select_pair_host.h  km_select_pair_*: the same for the two mate streams of a paired-end run, kept or dropped as
+//                  pairs (select_host.h's SelDev per mate, a Staging in and a TextDrain out per mate)
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
 #include <hip/hip_runtime.h>
@@ -70,6 +72,8 @@
 #include "scan_rule.h"
 #include "select_kernel.h"
 #include "select_rule.h"
+#include "select_pair_kernel.h"
+#include "select_pair_rule.h"
 
 using namespace kmd;
 
@@ -87,3 +91,4 @@ using namespace kmd;
 #include "dump_host.h"
 #include "scan_host.h"
 #include "select_host.h"
+#include "select_pair_host.h"

@@ -49,6 +49,7 @@ SYMBOLS = [
     "kmjf_cov_seqs", "kmjf_scan_text", "km_scan_kernel_ms",
     "km_select_create", "km_select_add_fastq", "km_select_stats", "km_select_destroy", "kmjf_fastq_hits",
     "km_select_kernel_ms",
+    "km_select_pair_create", "km_select_pair_add_fastq", "km_select_pair_stats", "km_select_pair_destroy",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
 ]
 
@@ -101,6 +102,13 @@ class SelectStats(C.Structure):
     """km_select_stats_t (include/kmgpu.h)."""
     _fields_ = [("records_in", C.c_uint64), ("records_out", C.c_uint64), ("bytes_in", C.c_uint64),
                 ("bytes_out", C.c_uint64), ("pieces", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class SelectPairStats(C.Structure):
+    """km_select_pair_stats_t (include/kmgpu.h)."""
+    _fields_ = [("pairs_in", C.c_uint64), ("pairs_out", C.c_uint64), ("bytes_in", C.c_uint64 * 2),
+                ("bytes_out", C.c_uint64 * 2), ("pieces", C.c_uint64), ("resent_bytes", C.c_uint64 * 2),
+                ("reserved", C.c_uint64 * 3)]
 
 
 class TextState(C.Structure):
@@ -300,6 +308,10 @@ def load():
         "km_select_destroy": [vp],
         "kmjf_fastq_hits": [vp, vp, u64, i32, vp, u64, C.POINTER(u64), vp],
         "km_select_kernel_ms": [C.POINTER(C.c_float)],
+        "km_select_pair_create": [vp, u32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(vp)],
+        "km_select_pair_add_fastq": [vp, vp, u64, vp, u64, i32, C.POINTER(u64), C.POINTER(u64)],
+        "km_select_pair_stats": [vp, C.POINTER(SelectPairStats)],
+        "km_select_pair_destroy": [vp],
         "km_device_count": [C.POINTER(i32)],
         "km_device_sync": [i32],
         "km_device_copy_GBs": [i32, u64, i32, C.POINTER(dbl)],
@@ -914,6 +926,68 @@ def select_kernel_ms():
     ms = (C.c_float * 4)()
     check(load().km_select_kernel_ms(ms))
     return {"front": float(ms[0]), "hits": float(ms[1]), "sizes": float(ms[2]), "gather": float(ms[3])}
+
+
+PAIR_RULES = {"any": 0, "both": 1, "sum": 2}     # KM_PAIR_ANY, KM_PAIR_BOTH, KM_PAIR_SUM
+
+
+class PairSelector:
+    """The mates of a paired-end run that hit a table, kept together on the GPU (km_select_pair_*, include/kmgpu.h):
+    record r of `data1` and record r of `data2` are pair r, kept iff (score >= min_hits) != invert with score =
+    max(h1, h2) for rule "any", min(h1, h2) for "both" and h1 + h2 for "sum"; mate 1's kept records go to `out1` and
+    mate 2's to `out2` (descriptors, or file objects with fileno()) byte for byte and in input order.  With check_names
+    the mates' names (without a "/1" or "/2" at the end) must agree.  `db` must stay open for as long as the selector
+    lives.  A context manager; close() releases the device side."""
+
+    def __init__(self, db, out1, out2, min_hits=1, invert=False, min_qual_char=None, rule="any", check_names=True,
+                 stream=None):
+        self._lib = load()
+        self._s = C.c_void_p()
+        self._db = db
+        if isinstance(rule, str) and rule not in PAIR_RULES:
+            raise KmError(4, "pair rule %r is none of 'any', 'both', 'sum'" % (rule,))       # KM_E_ARG
+        code = PAIR_RULES[rule] if isinstance(rule, str) else int(rule)
+        check(self._lib.km_select_pair_create(db._h, int(min_hits), int(bool(invert)), _qual_byte(min_qual_char or 0),
+                                              code, int(bool(check_names)), out_descriptor(out1), out_descriptor(out2),
+                                              C.c_void_p(stream or 0), C.byref(self._s)))
+        _LIVE_COUNTERS.add(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._s is not None and self._s.value:
+            self._lib.km_select_pair_destroy(self._s)
+        self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_fastq(self, data1, data2, final=False):
+        """4-line FASTQ text of mate 1 and of mate 2; returns (used1, used2), how many bytes of either were taken (whole
+        records that found their partner): pass the rest of each again in front of its next block.  What the call kept
+        is on the descriptors when it returns.  A malformed record, mates whose names differ and, at the final call,
+        streams of unequal record counts raise KmError (KM_E_FORMAT); the pieces before it are written."""
+        buf1, buf2 = _byte_view(data1), _byte_view(data2)
+        used1, used2 = C.c_uint64(), C.c_uint64()
+        check(self._lib.km_select_pair_add_fastq(self._s, ptr(buf1) if buf1.size else None, buf1.size,
+                                                 ptr(buf2) if buf2.size else None, buf2.size, int(bool(final)),
+                                                 C.byref(used1), C.byref(used2)))
+        return int(used1.value), int(used2.value)
+
+    def stats(self):
+        st = SelectPairStats()
+        check(self._lib.km_select_pair_stats(self._s, C.byref(st)))
+        out = {"pairs_in": int(st.pairs_in), "pairs_out": int(st.pairs_out), "pieces": int(st.pieces)}
+        for name in ("bytes_in", "bytes_out", "resent_bytes"):
+            out[name] = [int(v) for v in getattr(st, name)]
+        return out
 
 
 MERGE_MODES = {"sum": 0, "max": 1}         # KM_MERGE_SUM, KM_MERGE_MAX

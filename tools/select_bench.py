@@ -11,6 +11,10 @@ nothing in the first shape and nearly the whole input in the second.  Per shape:
                    read + write of a large device-to-device copy in the same run; group_GBs: the same over sizes +
                    scan + gather
   bytes_in / bytes_out / reads_in / reads_out / pieces
+`paired` holds `bait` and `bait -v` over the same reads as two mate files of half of them each
+(count.select_pair_files, rule any, names checked): wall_s, kernel_ms (both mates summed; "sizes" holds the pair's
+sizes, the name check and both scans, "gather" the one launch for both mates), pairs_in / pairs_out, bytes per mate,
+pieces, resent_bytes and resent_share = resent bytes / bytes_in.
 `bait_v_one_piece` is `bait -v` again with staging buffers (KM_COUNT_STAGE_BYTES) and blocks that hold the whole text,
 so that every kernel runs once over 64 MB;
 and once: the same text in the same blocks through Counter.add_fastq (counting its k-mers: the other consumer of the
@@ -80,6 +84,22 @@ def time_shape(db, path, invert, reps, block=kc.BLOCK):
     return out
 
 
+def time_paired(db, path1, path2, invert, reps, block=kc.BLOCK):
+    wall, kernel, stats = [], [], None
+    with open(os.devnull, "wb") as null1, open(os.devnull, "wb") as null2:
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            stats = kc.select_pair_files(db, [path1], [path2], null1, null2, invert=invert, block=block)
+            wall.append(time.perf_counter() - t0)
+            kernel.append(kmlib.select_kernel_ms())
+    best = min(range(reps), key=lambda i: wall[i])
+    bytes_in = sum(stats["bytes_in"])
+    return {"wall_s": wall[best], "wall_s_all": wall, "kernel_ms": kernel[best], "kernel_ms_all": kernel,
+            "bytes_per_s": bytes_in / wall[best], "pairs_in": stats["pairs_in"], "pairs_out": stats["pairs_out"],
+            "bytes_in": stats["bytes_in"], "bytes_out": stats["bytes_out"], "pieces": stats["pieces"],
+            "resent_bytes": stats["resent_bytes"], "resent_share": sum(stats["resent_bytes"]) / bytes_in}
+
+
 def time_counter(text, device, reps, block=kc.BLOCK):
     wall = []
     for _ in range(reps):
@@ -121,6 +141,13 @@ def main():
         time_shape(db, path, False, 1)                    # code object load, first allocations
         out["bait"] = time_shape(db, path, False, args.reps)
         out["bait_v"] = time_shape(db, path, True, args.reps)
+        half = (n_reads // 2) * (2 * READ + 7)            # the same text as two mate files of half the reads each
+        path1, path2 = os.path.join(tmp, "reads_1.fq"), os.path.join(tmp, "reads_2.fq")
+        text[:half].tofile(path1)
+        text[half:2 * half].tofile(path2)
+        time_paired(db, path1, path2, False, 1)
+        out["paired"] = {"bait": time_paired(db, path1, path2, False, args.reps),
+                         "bait_v": time_paired(db, path1, path2, True, args.reps)}
         out.update(time_counter(text, args.device, args.reps))      # (before the large buffers of the last shape)
         os.environ["KM_COUNT_STAGE_BYTES"] = str(text.size + 4096)
         time_shape(db, path, True, 1, block=text.size + 4096)

@@ -175,6 +175,13 @@ def rule_batches():
         long_n[::k] = b"N" * len(long_n[::k])
         out.append(("non-bases", k, True, [b"N" + random_bases(rng, 70) + b"N", bytes(long_n), b"AN"[: k - 1], b"acgtacgtacgtnacgtacgtacgtacgtacgtacgtacgt",
                                            random_bases(rng, 40) + b"N", b"N" + random_bases(rng, 40), b"", b"N", b""]))
+    # the structured corpus of tests/test_text_kernels_every_k.py, a few KB of it: k = 32 (no mask, keys above 2^63), even
+    # k (palindromes), k = 2 .. 4, 2k across 32 bits, homopolymers, microsatellites, both strands, non-bases at the ends
+    # of a lane's range
+    import test_text_kernels_every_k as every_k
+    for k in every_k.RULE_KS:
+        for canonical in (True, False):
+            out.append(("structured", k, canonical, every_k.structured_reads(k, small=True)))
     return out
 
 

@@ -197,6 +197,14 @@ def rule_cases():
         quals = [bytes(q) for q in quals]
         reads = [random_bases(rng, 60) for _ in range(300)]
         out.append(("quality", k, True, 1, 0, 53, fastq(reads, quals=quals, eol=b"\r\n", last_newline=False), reads[::3]))
+    # the structured corpus of tests/test_text_kernels_every_k.py, a few KB of it, baited with every third of its reads
+    import test_text_kernels_every_k as every_k
+    for k in every_k.RULE_KS:
+        reads = every_k.structured_reads(k, small=True)
+        quals = every_k.structured_quals(k, reads)
+        for canonical in (True, False):
+            out.append(("structured", k, canonical, 1, 0, 0, fastq(reads), reads[::3]))
+            out.append(("structured -v, quality", k, canonical, 2, 1, 43, fastq(reads, quals=quals, last_newline=False), reads[1::3]))
     return out
 
 

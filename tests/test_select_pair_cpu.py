@@ -310,6 +310,15 @@ def pair_rule_cases():
     out.append(("names differ", 1, 0, 0, "any", 1, t1, b"".join(recs[:211]) + b"@other\n" + recs[211].split(b"\n", 1)[1] + b"".join(recs[212:]), table))
     out.append(("mate 2 short", 1, 0, 0, "both", 1, t1, b"".join(recs[:-1]), table))
     out.append(("mate 1 short", 1, 1, 0, "any", 0, b"".join(recs[:-1]), t1, table))
+    # the structured corpus of tests/test_text_kernels_every_k.py, a few KB of it, as mate 1, and its reverse complement
+    # or random bases as mate 2; these cases carry their own k and canonical behind the table
+    import test_text_kernels_every_k as every_k
+    for k in every_k.RULE_KS:
+        t1, t2 = every_k.pair_case(k, small=True)
+        baits = [sm._content(s) for _, s, _, _ in sm.fastq_records(t1)][::3]
+        for canonical in (True, False):
+            rule = "sum" if canonical else "both"
+            out.append(("structured " + rule, 3 if rule == "sum" else 2, 0, 0, rule, 1, t1, t2, kmers_of(baits, k, canonical), k, canonical))
     return out
 
 
@@ -326,18 +335,20 @@ def test_pair_rule_program_under_sanitizers(tmp_path):
                            "-Wall", "-Werror", "-o", exe, os.path.join(HERE, "host", "select_pair_rule.cpp")])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     stages = [256, 4096]
-    for name, min_hits, invert, min_qual, rule, check_names, text1, text2, table in pair_rule_cases():
+    for case in pair_rule_cases():
+        name, min_hits, invert, min_qual, rule, check_names, text1, text2, table = case[:9]
+        k, canonical = case[9:] or (31, True)
         path = str(tmp_path / "in.bin")
-        pair_rule_input(path, 31, 1, min_hits, invert, min_qual, rule, check_names, table, stages, text1, text2)
+        pair_rule_input(path, k, int(canonical), min_hits, invert, min_qual, rule, check_names, table, stages, text1, text2)
         proc = subprocess.run([exe, path], capture_output=True, env=env, timeout=600)
         assert proc.returncode == 0 and proc.stdout.endswith(b"SELECT PAIR RULE OK\n"), (name, proc.stdout[-300:], proc.stderr[-3000:])
         assert b"ERROR: AddressSanitizer" not in proc.stderr and b"runtime error" not in proc.stderr, proc.stderr[-3000:]
         runs = parse_program_output(proc.stdout, stages)
         full = None                                               # what a run without the name check writes
         if "short" not in name:
-            full = model_pair_select(text1, text2, table, 31, True, min_hits, invert, min_qual, rule, False)
+            full = model_pair_select(text1, text2, table, k, canonical, min_hits, invert, min_qual, rule, False)
         try:
-            want = model_pair_select(text1, text2, table, 31, True, min_hits, invert, min_qual, rule, bool(check_names))
+            want = model_pair_select(text1, text2, table, k, canonical, min_hits, invert, min_qual, rule, bool(check_names))
             error = None
         except PairError as e:
             want, error = None, e
@@ -353,7 +364,7 @@ def test_pair_rule_program_under_sanitizers(tmp_path):
             elif error.kind == "names":
                 assert run["failure"] == ("NAMES", str(error.index)), ctx
                 recs1 = [b"".join(r) for r in sm.fastq_records(text1)]
-                kept = kept_pairs(text1, text2, table, 31, True, min_hits, invert, min_qual, rule)
+                kept = kept_pairs(text1, text2, table, k, canonical, min_hits, invert, min_qual, rule)
                 done = run["pairs"]                               # the pairs of the pieces before the failing one
                 assert 0 < done <= error.index, ctx
                 assert run["out"][0] == b"".join(recs1[r] for r in kept if r < done) and run["out"] == [
@@ -364,7 +375,7 @@ def test_pair_rule_program_under_sanitizers(tmp_path):
                 short = min(len(sm.fastq_records(text1)), len(sm.fastq_records(text2)))
                 cut1 = b"".join(b"".join(r) for r in sm.fastq_records(text1)[:short])
                 cut2 = b"".join(b"".join(r) for r in sm.fastq_records(text2)[:short])
-                assert run["out"] == list(model_pair_select(cut1, cut2, table, 31, True, min_hits, invert, min_qual, rule,
+                assert run["out"] == list(model_pair_select(cut1, cut2, table, k, canonical, min_hits, invert, min_qual, rule,
                                                             bool(check_names))), ctx
 
 

@@ -369,6 +369,12 @@ int km_batch_debug_stamps(km_batch_t* b, uint64_t* dst, uint64_t cap_words, uint
  * the pure-chain pass handed to k_graph, [2] flagged targets the epilogue of k_dfs left to k_graph, [3] a host counter: how
  * often, since the batch was made, its k_seed has run in another batch's walk launch (km_batch_pump's paired steps). */
 int km_batch_debug_counts(km_batch_t* b, uint32_t* out4);
+/* Diagnostics: a read-only look at an uploaded table — its directory (n_buckets + 1 words: bucket b owns the slots
+ * [2 dir[b], 2 dir[b+1])) to dir[dir_cap words] and its slots (16 bytes each: u64 tag, ~0 if empty, then four u16
+ * counts) to slots[slots_cap_bytes], copied synchronously.  *n_buckets / *n_slots always report the sizes; with dir
+ * and slots both NULL nothing else happens.  KM_E_STATE before the upload, KM_E_ARG if a capacity is too small. */
+int kmjf_debug_table(kmjf_t* h, uint32_t* dir, uint64_t dir_cap, void* slots, uint64_t slots_cap_bytes,
+                     uint64_t* n_buckets, uint64_t* n_slots);
 
 /* ---- linear_kmin -------------------------------------------------------------------------------
  * `km linear_kmin` (km/tools/linear_kmin.py:7-46) for a catalog: per target, the smallest k >= start at

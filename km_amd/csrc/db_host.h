@@ -328,6 +328,17 @@ extern "C" int kmjf_upload_from_device(kmjf_t* h, int device, const uint64_t* d_
     hipLaunchKernelGGL(k_dir_grow, dim3(grid_for((uint64_t)n_buckets, 256)), dim3(256), 0, st, caps,
                        (uint64_t)n_buckets, tv.cshift, lean_crowded);
   }
+  // the buckets the last insert did not list for k_table_settle: which of two groups took the first slot of their home
+  // pair is all the race decided there; tag order takes that out as well (settle_bits: as that insert left them)
+  if (n) {
+    TableView tv_slots = tv;
+    tv_slots.slots = slots;
+    hipLaunchKernelGGL(k_table_order_pairs, dim3(grid_for((uint64_t)n_buckets, 256)), dim3(256), 0, st, tv_slots, slots,
+                       settle_bits);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail_hip(KM_E_HIP, "table order pass failed", e);
+  }
   if (verbose)
     fprintf(stderr, "libkmgpu: table built in %d round(s): %llu slots for %llu groups, max_probe %u\n",
             rounds + 1, (unsigned long long)n_slots, meta[0], max_probe);
@@ -562,6 +573,22 @@ extern "C" int kmjf_load(const char* path, int device, kmjf_t** out) {
   if (rc != KM_OK) { delete h; return rc; }
   h->n_records = nz;
   *out = h;
+  return KM_OK;
+}
+
+// Diagnostics: the directory and the slots of an uploaded table as they lie in HBM (tests classify the buckets)
+extern "C" int kmjf_debug_table(kmjf_t* h, uint32_t* dir, uint64_t dir_cap, void* slots, uint64_t slots_cap_bytes,
+                                uint64_t* n_buckets, uint64_t* n_slots) {
+  if (!h || !n_buckets || !n_slots) return fail(KM_E_ARG, "null argument");
+  if (!h->d_slots) return fail(KM_E_STATE, "table not uploaded");
+  *n_buckets = h->n_buckets;
+  *n_slots = h->n_slots;
+  if (!dir && !slots) return KM_OK;
+  if (dir && dir_cap < (uint64_t)h->n_buckets + 1) return fail(KM_E_ARG, "directory buffer too small");
+  if (slots && slots_cap_bytes < h->n_slots * sizeof(Slot)) return fail(KM_E_ARG, "slot buffer too small");
+  HIPCHK(hipSetDevice(h->device));
+  if (dir) HIPCHK(hipMemcpy(dir, h->d_dir, ((uint64_t)h->n_buckets + 1) * 4, hipMemcpyDeviceToHost));
+  if (slots) HIPCHK(hipMemcpy(slots, h->d_slots, h->n_slots * sizeof(Slot), hipMemcpyDeviceToHost));
   return KM_OK;
 }
 

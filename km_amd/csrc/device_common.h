@@ -489,14 +489,14 @@ __device__ inline uint32_t bucket_of_wave(const TableView& t, uint64_t P) {
 // changed (the next bucket is loaded and evaluated) or the group does not exist.  A key never
 // leaves its bucket (probing wraps inside it), so "some slot of the bucket holds the tag" is exactly
 // the table's own answer.  Buckets of more than 64 * BUCKET_LANES_SETS slots are not held.
-constexpr uint32_t BUCKET_LANES_SETS = 7;          // slots per lane: buckets of up to 576 slots are held (a crowded
-                                                   // bucket of the usual size, 4 * 128 + NC = 544 slots, fits)
+constexpr uint32_t BUCKET_LANES_SETS = 7;          // slots per lane: buckets of up to 448 slots are held (a crowded bucket
+                                                   // of the lean rule, 2 * 192 + NC = 416 slots, fits; 4 * 128 + NC = 544 does not)
 constexpr uint32_t SLOT_SINGLE = 4u, SLOT_HINT = 8u;
 struct BucketLanes {
   uint64_t tag[BUCKET_LANES_SETS];                           // lane j, set i: slot 64 i + j (EMPTY past the end)
   uint32_t info[BUCKET_LANES_SETS];                          // child base | SLOT_SINGLE | SLOT_HINT | count << 16
-  // (round 3 also kept the tag of the group the walk looks up next: two more registers per set, i.e. buckets of 256
-  // slots instead of 576 in the same registers; the walk works that tag out from the child, a dozen scalar instructions)
+  // (round 3 also kept the tag of the group the walk looks up next: two more registers per set, i.e. 4 sets, buckets of
+  // 256 slots, instead of 7 sets, 448 slots, in about the same registers; the walk works that tag out from the child, a dozen scalar instructions)
   uint32_t bucket, S;    // wave-uniform
   bool valid, resident;
 };
@@ -553,7 +553,7 @@ struct SlotHit { uint32_t info; bool hit; };
 // (nested, so that a hit leaves through one branch: a flat loop over the sets makes the compiler chain
 // an exit flag through every later set — sixteen taken branches behind a hit in the first one)
 // (no test of the set against the bucket's size: the sets a bucket does not reach hold EMPTY tags, which no
-// group has — nine scalar compares a step otherwise, and a miss, which looks at every set, is a bucket change)
+// group has — one scalar compare per set and step otherwise, and a miss, which looks at every set, is a bucket change)
 template <uint32_t I>
 __device__ inline void bucket_find_from(const BucketLanes& b, uint64_t tag, SlotHit& h) {
   if constexpr (I < BUCKET_LANES_SETS) {

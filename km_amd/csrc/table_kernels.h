@@ -488,6 +488,26 @@ __global__ __launch_bounds__(256) void k_table_settle(TableView t, Slot* slots, 
   for (uint32_t i = tid; i < S; i += 256) base[i] = A[i];
 }
 
+// Order pass.  k_table_settle takes the race out of the buckets that hold a key outside its home pair; in every
+// other bucket each key sits in its home pair, and all the race still decided is which of two groups sharing a pair
+// took its first slot.  One thread per such bucket puts the two slots of every aligned pair in tag order (EMPTY, the
+// largest value, last: a lookup that meets an empty first slot stops there).  Both groups are at home in the pair and a
+// lookup reads the whole pair, so no result changes; with it the table read back (kmjf_debug_table) is a function of the
+// records.  Buckets on the settle list are skipped: their probe sequences run across the pairs.
+__global__ void k_table_order_pairs(TableView t, Slot* slots, const uint32_t* settle_bits) {
+  for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < t.n_buckets;
+       b += (uint64_t)gridDim.x * blockDim.x) {
+    if ((settle_bits[b >> 5] >> (b & 31)) & 1u) continue;
+    const uint32_t lo = t.dir[b], hi = t.dir[b + 1];
+    uint4* p = reinterpret_cast<uint4*>(slots + 2ull * lo);
+    for (uint64_t i = 0; i < (uint64_t)(hi - lo); ++i) {
+      const uint4 a0 = p[2 * i], a1 = p[2 * i + 1];
+      const uint64_t t0 = ((uint64_t)a0.y << 32) | a0.x, t1 = ((uint64_t)a1.y << 32) | a1.x;
+      if (t0 > t1) { p[2 * i] = a1; p[2 * i + 1] = a0; }
+    }
+  }
+}
+
 // Jellyfish.query for a batch (km/utils/Jellyfish.py:47-53; the loop of
 // common.get_cov, km/utils/common.py:73-92).
 __global__ void k_query(TableView t, const uint64_t* kmers, uint64_t n, uint32_t* out) {

@@ -1735,7 +1735,10 @@ __device__ __forceinline__ void dfs_body(const WalkArgs a, const uint32_t bid, c
           const bool chained = e + 1 < m && (Xn >> 2) == S && !next_head;
           if (e < m && !chained) {
             uint32_t nx = NONE, n1 = NONE;
-            const uint32_t sc = nodes_with_prefix(S, NONE, &nx, &n1);
+            // (e itself aside: a homopolymer k-mer is behind its own suffix, and the reference's graph has no edge from
+            // a node to itself — `if i != j`, km/utils/MutationFinder.py:530 — so a one-node bubble c^k between
+            // x c^(k-1) and c^(k-1) y is no loop)
+            const uint32_t sc = nodes_with_prefix(S, e, &nx, &n1);
             if (sc == 2) {
               // two nodes behind the end of a bubble: a reference node b and a walk node — the bubble's OWN head,
               // if this is a loop (a tandem duplication a little shorter than k: the head shares its prefix with

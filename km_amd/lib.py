@@ -35,6 +35,7 @@ SYMBOLS = [
     "kmjf_query_batch_dev", "kmjf_children_batch_dev", "km_batch_create", "km_batch_destroy",
     "km_batch_set_targets", "km_batch_set_targets_dev", "km_batch_run", "km_batch_sync",
     "km_batch_sizes", "km_batch_fetch", "km_batch_result", "km_batch_timings", "km_batch_graph_log", "km_batch_pump", "km_batch_debug_stamps", "km_batch_debug_counts",
+    "kmjf_debug_table",
     "km_device_sync", "km_device_copy_GBs", "km_probe_bench",
     "km_report_rows", "km_report_free", "km_linear_kmin", "km_strerror", "km_last_error",
     "km_counter_create", "km_counter_add_bases", "km_counter_add_text", "km_counter_stats", "km_counter_finish",
@@ -260,6 +261,7 @@ def load():
         "km_batch_pump": [C.POINTER(vp), C.POINTER(vp), i32, i32, i32],
         "km_batch_debug_stamps": [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)],
         "km_batch_debug_counts": [vp, C.POINTER(C.c_uint32)],
+        "kmjf_debug_table": [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)],
         "km_report_rows": [C.POINTER(ReportIn), C.POINTER(vp), C.POINTER(C.POINTER(C.c_uint64)),
                            C.POINTER(C.POINTER(C.c_int32))],
         "km_linear_kmin": [i32, vp, vp, u32, i32, vp, vp, vp, vp],
@@ -506,6 +508,16 @@ class Database:
                                             int(n_cutoff), int(bool(forward)), ptr(mask),
                                             ptr(counts4)))
         return mask, counts4
+
+    def debug_table(self):
+        """kmjf_debug_table: the uploaded table as it lies in HBM -> (dir uint32[n_buckets + 1], tag uint64[n_slots],
+        counts uint16[n_slots, 4]); bucket b owns the slots [2 dir[b], 2 dir[b + 1]), an empty slot has tag ~0."""
+        nb, ns = C.c_uint64(), C.c_uint64()
+        check(self._lib.kmjf_debug_table(self._h, None, 0, None, 0, C.byref(nb), C.byref(ns)))
+        dir_ = np.zeros(nb.value + 1, np.uint32)
+        slots = np.zeros(ns.value, np.dtype([("tag", np.uint64), ("c", np.uint16, (4,))]))
+        check(self._lib.kmjf_debug_table(self._h, ptr(dir_), dir_.size, ptr(slots), slots.nbytes, C.byref(nb), C.byref(ns)))
+        return dir_, slots["tag"].copy(), slots["c"].copy()
 
     def query_text(self, kmers, out_fd, stream=None):
         """kmjf_query_text: one "MER COUNT" line per k-mer (uint64, as given: canonicalised by the caller for a

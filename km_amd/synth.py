@@ -579,6 +579,19 @@ def end_duplication_case(k, seed=0):
     return {"name": "enddup%d" % k, "target": T, "reads": [(T, 60), (T + T[-(k + 5):], 30)], "k": k}
 
 
+def homopolymer_insertion_case(k, base, seed=0):
+    """One more `base` in a run of k - 1 of them: the variant's only new k-mer is the homopolymer base^k, a one-node
+    bubble between x base^(k-1) and base^(k-1) y whose node is behind its own suffix (the reference's graph has no
+    edge from a node to itself: km/utils/MutationFinder.py:530)."""
+    rng = np.random.default_rng(8600 + 43 * k + 5 * "ACGT".index(base) + seed)
+    while True:
+        left, right = random_seq(rng, k + 3), random_seq(rng, k + 3)
+        T = left + base * (k - 1) + right
+        V = left + base * k + right
+        if left[-1] != base and right[0] != base and not has_repeated_kmer(T, k) and not has_repeated_kmer(V, k):
+            return {"name": "homo_%s%d" % (base, k), "target": T, "reads": [(T, 60), (V, 30)], "k": k}
+
+
 def dense_counts(rng, n):
     """30 % in 100 .. 70 000 (both sides of the 16-bit escape), the rest in 1 .. 5 (around `count`)."""
     c = rng.integers(1, 6, size=n)

@@ -132,7 +132,8 @@ def bubbles_shape(kmers, n_ref, allow_back=False, allow_loop=False):
         a, s = head_of[e], e
         looped = False
         while True:
-            behind = by_prefix.get(kmers[e][1:], [])
+            # (e itself aside: the reference's graph has no edge from a node to itself, MutationFinder.py:530)
+            behind = [x for x in by_prefix.get(kmers[e][1:], []) if x != e]
             if allow_loop and len(behind) == 2 and s in behind and min(behind) == a + 1:
                 b, looped = a + 1, True                 # the end of the bubble points at b and at its own head
                 break
@@ -292,3 +293,22 @@ def test_closed_form_with_looped_bubbles(k):
         got = [tuple(p) for p in ko.graph_paths(kmers, n_ref)]
         assert got == sorted(want), (k, trial, shape, n_ref, len(kmers))
     assert n_loop >= 15 and n_loop_mixed >= 3, (n_loop, n_loop_mixed)
+
+
+@pytest.mark.parametrize("k", [11, 13, 21, 31, 32])
+def test_a_homopolymer_node_is_no_loop(k):
+    """One more base in a run of k - 1 equal ones: the bubble is the single k-mer c^k, which is behind its own suffix.
+    The reference's graph has no edge from a node to itself (km/utils/MutationFinder.py:530), so this is an ordinary
+    forward bubble with b = a + 1 — two paths, none through the bubble twice."""
+    for base in "ACGT":
+        case = synth.homopolymer_insertion_case(k, base)
+        keys, counts = synth.records_from_reads(case["reads"], k)
+        db = ko.KmerDB(None, cutoff=0.05, n_cutoff=5, records={"k": k, "canonical": True, "keys": keys, "counts": counts})
+        mers = ko.ref_kmers(case["target"], case["name"], k)
+        kmers = list(ko.walk(mers, db).keys())
+        n_ref = len(mers)
+        assert kmers[n_ref:] == [base * k]
+        a = case["target"].index(base * (k - 1)) - 1
+        assert bubbles_shape(kmers, n_ref, allow_back=True, allow_loop=True) == [(a, n_ref, n_ref, a + 1, False)]
+        want = [tuple(range(n_ref)), tuple(range(a + 1)) + (n_ref,) + tuple(range(a + 1, n_ref))]
+        assert [tuple(p) for p in ko.graph_paths(kmers, n_ref)] == sorted(want), (k, base)

@@ -470,6 +470,28 @@ def test_statuses_of_degenerate_targets(k):
     db.close()
 
 
+@gpu
+@pytest.mark.parametrize("k", WALK_KS)
+def test_homopolymer_node_between_two_target_kmers(k):
+    """One more base in a run of k - 1 equal ones of the target: the only discovered node is c^k, a one-node bubble
+    whose k-mer is behind its own suffix.  No path goes through it twice: the reference's graph has no edge from a
+    node to itself (the epilogue of k_dfs once took that for a looped tandem duplication)."""
+    for base in "ACGT":
+        case = synth.homopolymer_insertion_case(k, base)
+        keys, counts, co, py = _tables(case)
+        c = _c_want(co, case["target"])
+        p = _py_want(py, case["target"], case["name"], k)
+        for field in ("status", "kmers", "counts", "probes", "paths", "min_cov"):
+            assert c[field] == p[field], (case["name"], field)
+        n_ref = len(case["target"]) - k + 1
+        a = case["target"].index(base * (k - 1)) - 1
+        assert c["kmers"][n_ref:] == [km.pack_str(base * k)]
+        assert c["paths"] == sorted([list(range(n_ref)), list(range(a + 1)) + [n_ref] + list(range(a + 1, n_ref))])
+        db = kmlib.Database.from_records(keys, counts, k).upload(0)
+        _against_c(db, co, k, [case["target"]], case["name"], wants=[c])
+        db.close()
+
+
 def _all_t_case():
     k = 32
     rng = np.random.default_rng(9600)

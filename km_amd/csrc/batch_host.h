@@ -72,8 +72,8 @@ CreateOptions read_create_options() {
 // ---------------------------------------------------------------------------- batch
 namespace {
 
-// (FAST_EXTRA, FAST_LDS_LIMIT, FAST_BCAP_MAX, what fits the fast tier, and round_up: tier_geometry.h)
-constexpr uint32_t FAST_FCAP_MAX = 4096;      // stack frames per target in the fast tier's scratch
+// (FAST_EXTRA, FAST_LDS_LIMIT, FAST_BCAP_MAX, FAST_FCAP_MAX, what fits the fast tier and its sizes, and round_up:
+// tier_geometry.h)
 constexpr uint32_t LOOP_LOG_CAP = 4096;       // loop breaks of a batch kept for km_batch_graph_log (the rest is counted only)
 constexpr uint32_t BIG_DEV_SLOTS = 32;        // targets per run the device's own large tier takes (the rest: the host's)
 constexpr uint64_t BIG_DEV_MAX_BYTES = 1ull << 30;   // ... unless their node storage would exceed this (huge -n)
@@ -656,30 +656,21 @@ static void fill_graph_args(km_batch* b, GraphArgs& g) {
 static void fast_geometry(km_batch* b) {
   const int k = b->db->k;
   const uint32_t max_nref = b->max_len >= (uint32_t)k ? b->max_len - k + 1 : 1;
-  const uint32_t bcap = std::min<uint32_t>(b->p.max_break, FAST_BCAP_MAX - 1) + 1;
-  uint32_t nref = max_nref;
-  if (!fast_tier_fits(k, nref, bcap)) {
-    uint32_t lo = 1, hi = max_nref;          // fits(lo) holds: a 1-k-mer target always fits
-    while (lo + 1 < hi) {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (fast_tier_fits(k, mid, bcap)) lo = mid; else hi = mid;
-    }
-    nref = lo;
-  }
-  const uint32_t len = nref + (uint32_t)k - 1;
+  const FastGeometry fg = fast_tier_geometry(k, max_nref, b->p.max_stack, b->p.max_break);
+  const uint32_t nref = fg.nref;
   WalkArgs& wa = b->wa;
   fill_walk_args(b, wa);
-  wa.hs_cap = walk_hs_cap(nref);
-  wa.pcap = walk_pcap(nref);
-  wa.words_cap = words_cap_for(len);
-  wa.fcap = round_up(std::min<uint32_t>(b->p.max_stack, FAST_FCAP_MAX - 2) + 2, 2);
-  wa.bcap = bcap;
+  wa.hs_cap = fg.hs_cap;
+  wa.pcap = fg.pcap;
+  wa.words_cap = fg.words_cap;
+  wa.fcap = fg.fcap;
+  wa.bcap = fg.bcap;
   wa.f_stride = walk_frame_bytes(wa.fcap);
   b->walk_lds = (uint32_t)walk_lds_bytes(wa.hs_cap, wa.words_cap, wa.bcap, wa.pcap, 2);
   GraphArgs& ga = b->ga;
   fill_graph_args(b, ga);
-  ga.ncap = nref + FAST_EXTRA + 2;
-  ga.hcap = graph_hcap(ga.ncap);
+  ga.ncap = fg.ncap;
+  ga.hcap = fg.hcap;
   ga.words_cap = wa.words_cap;
   b->graph_lds = (uint32_t)graph_ws_bytes<uint16_t>(ga.ncap, ga.hcap, ga.words_cap);
   ga.hcap_pure = 64;                                             // position table at load <= 1/4 (graph_kernel.h: k_graph_pure)
@@ -1244,7 +1235,10 @@ static int run_big_walk(km_batch* b, const std::vector<uint32_t>& ids, hipStream
   });
 }
 
-static int run_big_graph(km_batch* b, const std::vector<uint32_t>& ids, hipStream_t st) {
+// `by_edges`: workspaces sized by the most edges a target can have, 4 per node + 2, not by its nodes.  k_graph keeps
+// one candidate edge per path in a list of ncap entries; a dense graph (small k: most of the 4^k k-mers are nodes,
+// every node has several successors) has more of them than nodes and gets T_INTERNAL from the first pass.
+static int run_big_graph(km_batch* b, const std::vector<uint32_t>& ids, hipStream_t st, bool by_edges = false) {
   const uint32_t nb = (uint32_t)ids.size();
   KMCHK(b->big.d_big_ids.alloc(nb));
   HIPCHK(hipMemcpyAsync(b->big.d_big_ids.p, ids.data(), (uint64_t)nb * 4, hipMemcpyHostToDevice, st));
@@ -1252,7 +1246,8 @@ static int run_big_graph(km_batch* b, const std::vector<uint32_t>& ids, hipStrea
   for (uint32_t t : ids) max_nodes = std::max(max_nodes, b->t.h_n_nodes[t]);
   GraphArgs g;
   fill_graph_args(b, g);
-  big_graph_geometry(b, g, max_nodes + 2);
+  if (by_edges && max_nodes > 0x0FFFFFF0u) return fail(KM_E_NOMEM, "graph too large");
+  big_graph_geometry(b, g, by_edges ? 4 * (max_nodes + 2) : max_nodes + 2);
   return run_in_slices(b, nb, g.g_stride, st, [&](unsigned char* ws, uint32_t first, uint32_t cnt) {
     g.g_ws = ws;
     g.tids = b->big.d_big_ids.p + first;
@@ -1338,6 +1333,12 @@ extern "C" int km_batch_sync(km_batch_t* b) {
       if (!todo.empty()) {
         KMCHK(run_big_graph(b, todo, st));
         KMCHK(pull_status(b, st));
+        std::vector<uint32_t> dense;          // more candidate edges than nodes: once more, sized by the edges
+        for (uint32_t t : todo) if (b->t.h_status[t] == T_OK && b->t.h_gstatus[t] == T_INTERNAL) dense.push_back(t);
+        if (!dense.empty()) {
+          KMCHK(run_big_graph(b, dense, st, true));
+          KMCHK(pull_status(b, st));
+        }
         changed = true;
       }
       if (!b->paths.h_overflow) break;

@@ -423,6 +423,9 @@ __global__ __launch_bounds__(GRAPH_THREADS) void k_graph(GraphArgs a0) {
   if (tid == 0) a.t_refmax[t] = NOT_BARE;
   const uint32_t n = m + 2, src = m, snk = m + 1;
   const uint32_t ncap = a.ncap, hcap = a.hcap;
+  // (LDS tier: a target whose walk stayed in its tier has m <= n_ref + FAST_EXTRA, so n <= ncap — with equality for the
+  // batch's longest target at exactly FAST_EXTRA new nodes — and 3 n <= 2 hcap follows from hcap >= ncap + ncap / 2 + 1:
+  // neither fires there, tests/test_lds_tier_edges.py checks both over every target length the tier accepts)
   if (n > ncap || (uint64_t)3 * n > (uint64_t)2 * hcap || (!BIG && n >= 0xFFFFu)) {
     if (tid == 0) { a.g_status[t] = (BIG && !a0.tids_n) ? T_INTERNAL : T_NEEDS_BIG; a.t_npaths[t] = 0; a.t_pathbase[t] = 0; a.t_nruns[t] = 0; hand_to_big(); }
     return;
@@ -1112,6 +1115,9 @@ __global__ __launch_bounds__(GRAPH_THREADS) void k_graph(GraphArgs a0) {
   __syncthreads();
   if (tid == 0) { a.t_eremoved[t] = scal[7]; a.t_enonref[t] = scal[2] - scal[7]; }
   const uint32_t n_cand = scal[0];
+  // (reachable in both tiers: nothing bounds the candidates, one per path, by the nodes — a dense graph at small k has
+  // several per node.  The large tier's host pass then comes once more with workspaces sized by the edges, 4 per node:
+  // batch_host.h: run_big_graph.  tests/test_lds_tier_edges.py sits at n_cand == ccap and at ccap + 1.)
   if (n_cand > ccap) {
     if (tid == 0) { a.g_status[t] = (BIG && !a0.tids_n) ? T_INTERNAL : T_NEEDS_BIG; a.t_npaths[t] = 0; a.t_pathbase[t] = 0; a.t_nruns[t] = 0; hand_to_big(); }
     return;

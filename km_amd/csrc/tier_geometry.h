@@ -1,8 +1,9 @@
 // tier_geometry.h — what the LDS-resident ("fast") tier of the walk and graph kernels can hold: its constants and
 // the one predicate km_batch's geometry (batch_host.h: fast_geometry) bisects over.  Plain host arithmetic on the
 // kernels' own size functions, kept apart from km_batch so that a host program can ask it too
-// (tests/host/lds_tier_limit.hip).
+// (tests/host/lds_tier_limit.hip, tests/host/walk_geometry.hip).
 #pragma once
+#include <algorithm>
 #include "graph_kernel.h"
 #include "walk_kernel.h"
 
@@ -33,6 +34,33 @@ static bool fast_tier_fits(int k, uint32_t nref, uint32_t bcap) {
   return kmd::walk_lds_bytes(hs, wc, bcap, walk_pcap(nref), 2) <= FAST_LDS_LIMIT &&
          kmd::graph_ws_bytes<uint16_t>(ncap, hcap, wc) <= FAST_LDS_LIMIT && ncap < 0xFFFF &&
          (uint64_t)hcap * 4 + (uint64_t)wc * 8 <= FAST_LDS_LIMIT;   // (k_graph_pure hands over what its own table cannot hold)
+}
+
+constexpr uint32_t FAST_FCAP_MAX = 4096;      // stack frames per target in the fast tier's scratch
+
+// the sizes of the fast tier for a batch whose longest target has `max_nref` k-mers: what km_batch launches k_dfs and
+// k_graph with (batch_host.h: fast_geometry) and what tests/host/walk_geometry.hip prints
+struct FastGeometry { uint32_t nref, hs_cap, pcap, words_cap, fcap, bcap, ncap, hcap; };
+static FastGeometry fast_tier_geometry(int k, uint32_t max_nref, uint32_t max_stack, uint32_t max_break) {
+  FastGeometry g;
+  g.bcap = std::min<uint32_t>(max_break, FAST_BCAP_MAX - 1) + 1;
+  g.fcap = round_up(std::min<uint32_t>(max_stack, FAST_FCAP_MAX - 2) + 2, 2);
+  uint32_t nref = max_nref;
+  if (!fast_tier_fits(k, nref, g.bcap)) {
+    uint32_t lo = 1, hi = max_nref;          // fits(lo) holds: a 1-k-mer target always fits
+    while (lo + 1 < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (fast_tier_fits(k, mid, g.bcap)) lo = mid; else hi = mid;
+    }
+    nref = lo;
+  }
+  g.nref = nref;
+  g.hs_cap = walk_hs_cap(nref);
+  g.pcap = walk_pcap(nref);
+  g.words_cap = words_cap_for(nref + (uint32_t)k - 1);
+  g.ncap = nref + FAST_EXTRA + 2;
+  g.hcap = graph_hcap(g.ncap);
+  return g;
 }
 
 }  // namespace

@@ -1575,6 +1575,13 @@ __device__ __forceinline__ void dfs_body(const WalkArgs a, const uint32_t bid, c
               slot = node_find(child, &found);
               if (slot < 0 || found) { st = T_INTERNAL; break; }
             }
+            // (neither frame guard fires in the fast tier's everyday geometry — tests/test_lds_tier_edges.py shows it for
+            // every target length the tier accepts.  depth + 1 <= max_stack was checked above and fcap >= max_stack + 2
+            // while max_stack <= 4094; a deeper stack would need 4 096 live entries of a set whose limit stays below
+            // 1 000.  bsp <= max_break < bcap while max_break <= 511; with max_break >= 513 the 513th branch frame
+            // does get here, on a target whose set has room for 512 live frames and one more beside its losers,
+            // n_losers + 513 <= set_limit — possible from 1 028 k-mers on (set_limit 528), for a target that loses
+            // next to no slot of its position table: the comb of that file.)
             if (depth >= a.fcap) { st = BIG ? T_INTERNAL : T_NEEDS_BIG; break; }   // fast tier: bounded frames
             if (mask != 0) {
               if (bsp >= a.bcap) { st = BIG ? T_INTERNAL : T_NEEDS_BIG; break; }

@@ -272,18 +272,23 @@ def test_tie_cases_really_tie(k):
 
 # ------------------------------------------------------------------ CPU: the margin as arithmetic
 @functools.lru_cache(maxsize=None)
-def _lds_tier_program():
-    """tests/host/lds_tier_limit.hip, compiled once per session (host code only; hipcc is what builds the library)."""
+def _host_program(name):
+    """tests/host/<name>.hip, compiled once per session (host code only; hipcc is what builds the library).
+    tests/test_lds_tier_edges.py uses it too."""
     import atexit
     import tempfile
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     assert os.path.exists(hipcc)
-    tmp = tempfile.mkdtemp(prefix="km_lds_tier_")
+    tmp = tempfile.mkdtemp(prefix="km_%s_" % name)
     atexit.register(shutil.rmtree, tmp, ignore_errors=True)
-    exe = os.path.join(tmp, "lds_tier_limit")
+    exe = os.path.join(tmp, name)
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-o", exe,
-                           os.path.join(ROOT, "tests", "host", "lds_tier_limit.hip")])
+                           os.path.join(ROOT, "tests", "host", name + ".hip")])
     return exe
+
+
+def _lds_tier_program():
+    return _host_program("lds_tier_limit")
 
 
 @functools.lru_cache(maxsize=None)

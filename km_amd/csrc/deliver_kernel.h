@@ -263,7 +263,7 @@ __global__ __launch_bounds__(OUT_SCAN_THREADS) void k_out_scan(OutArgs a) {
 }
 
 // lexicographic order of two run-length encoded index sequences
-__device__ inline bool rle_less(const uint32_t* sa, const uint32_t* la, uint32_t na,
+__host__ __device__ inline bool rle_less(const uint32_t* sa, const uint32_t* la, uint32_t na,
                                 const uint32_t* sb, const uint32_t* lb, uint32_t nb) {
   uint32_t ia = 0, ib = 0, oa = 0, ob = 0;
   while (ia < na && ib < nb) {

@@ -57,8 +57,11 @@ static int finish_result(km_batch* b, bool need_full) {
       KMCHK(km_batch_sync(b));
     }
     HIPCHK(hipStreamSynchronize(st));
-    // (2: everything is final, only the tail is larger than the buffer)
-    KMCHK(ensure_out(b, nh == 2ull ? T[OT_TAIL_BYTES] + 4096 : default_tail_bytes(b, b->nodes.node_pool_used, b->nodes.node_pool_used)));
+    // (2: everything is final, only the tail is larger than the buffer.  A tail of 16-bit counts is sized for the
+    // 32-bit form, 2 more bytes per node and at most 16 of alignment: should the escape list overflow, that form
+    // follows, and a buffer grown by an eighth would send it round this loop once more)
+    KMCHK(ensure_out(b, nh == 2ull ? T[OT_TAIL_BYTES] + (b->out.count16 ? 2 * T[OT_N_NODES] + 16 : 0) + 4096
+                                   : default_tail_bytes(b, b->nodes.node_pool_used, b->nodes.node_pool_used)));
     T = reinterpret_cast<const unsigned long long*>(b->out.h_out + L.totals);
     KMCHK(enqueue_deliver(b, st, b->out.lean, b->out.count16));
   }

@@ -1,18 +1,11 @@
 // kmin_host.h — km_linear_kmin (host part of kmgpu.hip; device side: kmin_kernel.h)
 // ------------------------------------------------------------------ linear_kmin
 // km/tools/linear_kmin.py:7-46 for a whole catalog: one launch per staging chunk (kmin_kernel.h), then the
-// closed form of DESIGN.md §9 on the host.
+// closed form of DESIGN.md §9 on the host (kmin_rule.h).
+#include "kmin_rule.h"
+
 namespace {
 constexpr uint64_t KMIN_STAGE_BYTES = 256ull << 20;   // staged text per launch (a longer target goes alone)
-
-int32_t kmin_closed_form(uint64_t n, int32_t start, uint64_t R, uint8_t* flag) {
-  if (n == 0) { *flag = 0; return start <= 0 ? 0 : start - 1; }
-  if (R == 0) *flag = n >= 3;                          // k = 1: every (k-1)-mer is ""
-  if ((int64_t)start - 1 >= (int64_t)n) return start - 1;   // the reference's loop never runs
-  const int64_t lo = std::max<int64_t>(start, (int64_t)R + 1);
-  if (lo > (int64_t)R + 1) return (int32_t)lo;
-  return (int32_t)(*flag ? std::min<uint64_t>(R + 2, n) : R + 1);
-}
 }  // namespace
 
 extern "C" int km_linear_kmin(int device, const uint8_t* bases, const uint64_t* base_off, uint32_t n_targets,
@@ -100,7 +93,7 @@ extern "C" int km_linear_kmin(int device, const uint8_t* bases, const uint64_t* 
     for (uint32_t i = 0; i < nt; ++i) {
       const uint64_t R = h_keys[i] >> 1;
       uint8_t flag = (uint8_t)(h_keys[i] & 1);
-      kmin[t0 + i] = kmin_closed_form(h_len[i], start, R, &flag);
+      kmin[t0 + i] = kmlin::kmin_closed_form(h_len[i], start, R, &flag);
       if (longest_repeat) longest_repeat[t0 + i] = (int32_t)R;
       if (nonexempt) nonexempt[t0 + i] = flag;
     }

@@ -43,30 +43,17 @@ def feed_file(counter, path, block=BLOCK, min_qual_char=None):
     """One file through counter.add_text in blocks, the unconsumed tail carried in front of the next block.
     With min_qual_char (not None) a file whose first non-blank byte is '@' goes through counter.add_fastq with
     that quality threshold instead, from that byte on; a FASTA file has no qualities and takes add_text."""
-    fh, close = _open(path)
+    blocks = _Blocks(path, block, sniff=None if min_qual_char is None else "report")
     try:
-        tail = b""
-        add = None if min_qual_char is not None else counter.add_text
-        while True:
-            data = fh.read(block)
-            if not data:
-                break
-            buf = tail + data if tail else data
-            if add is None:
-                buf = buf.lstrip(b"\r\n")
-                if not buf:
-                    continue
-                if buf[:1] == b"@":
-                    def add(text, final, _q=min_qual_char):
-                        return counter.add_fastq(text, final=final, min_qual_char=_q)
-                else:
-                    add = counter.add_text
-            used = add(buf, final=False)
-            tail = buf[used:]
-        (add or counter.add_text)(tail, final=True)
+        def add(text, final):
+            if blocks.fastq:
+                return counter.add_fastq(text, final=final, min_qual_char=min_qual_char)
+            return counter.add_text(text, final=final)
+        for buf in blocks:
+            blocks.used(add(buf, final=False))
+        add(blocks.tail, final=True)
     finally:
-        if close:
-            fh.close()
+        blocks.close()
 
 
 def count_files(paths, k=31, canonical=True, lower_count=1, device=0, expected_distinct=0, keep_counter=False,
@@ -118,14 +105,16 @@ def _preflight(paths):
 
 
 class _Blocks:
-    """One FASTQ file as the blocks a selector takes: next() -> the unconsumed tail with the next block of the file
-    behind it (leading blank lines dropped), used(n) says how much of it was taken; done: the file has been read to
-    its end, so what next() returns is all there will be."""
+    """The only reader of a file in blocks: next() -> the unconsumed tail with the next block of the file behind it,
+    used(n) says how much of it was taken; done: the file has been read to its end, so what next() returns is all there
+    will be.  Iterating yields next() until then.  `sniff` looks at the first non-blank byte, once the leading blank
+    lines are dropped: "raise" takes 4-line FASTQ only (ValueError unless it is '@'), "report" says in `fastq` whether
+    it is '@'; None passes the file on as it is."""
 
-    def __init__(self, path, block):
-        self.path, self.block = path, block
+    def __init__(self, path, block, sniff="raise"):
+        self.path, self.block, self.sniff = path, block, sniff
         self.fh, self.close_it = _open(path)
-        self.tail, self.started, self.done = b"", False, False
+        self.tail, self.started, self.done, self.fastq = b"", sniff is None, False, False
 
     def next(self):
         while not self.done:
@@ -138,12 +127,20 @@ class _Blocks:
                 buf = buf.lstrip(b"\r\n")
                 if not buf:
                     continue
-                if buf[:1] != b"@":
+                self.fastq = buf[:1] == b"@"
+                if not self.fastq and self.sniff == "raise":
                     raise _not_fastq(self.path)
                 self.started = True
             self.tail = buf
             break
         return self.tail
+
+    def __iter__(self):
+        while True:
+            buf = self.next()
+            if self.done:
+                return
+            yield buf
 
     def used(self, n):
         self.tail = self.tail[n:]
@@ -236,29 +233,15 @@ def select_files(db, paths, out=None, min_hits=1, invert=False, min_qual_char=No
     with _text_out(out) as fd:
         with _lib.Selector(db, fd, min_hits=min_hits, invert=invert, min_qual_char=min_qual_char) as sel:
             for path in paths:
-                fh, close = _open(path)
+                blocks = _Blocks(path, block)
                 try:
-                    tail, started = b"", False
-                    while True:
-                        data = fh.read(block)
-                        if not data:
-                            break
-                        buf = tail + data if tail else data
-                        if not started:
-                            buf = buf.lstrip(b"\r\n")
-                            if not buf:
-                                continue
-                            if buf[:1] != b"@":
-                                raise _not_fastq(path)
-                            started = True
-                        used = sel.add_fastq(buf, final=False)
-                        tail = buf[used:]
-                    sel.add_fastq(tail, final=True)          # (always: an empty one still ends the file's stream)
+                    for buf in blocks:
+                        blocks.used(sel.add_fastq(buf, final=False))
+                    sel.add_fastq(blocks.tail, final=True)   # (always: an empty one still ends the file's stream)
                 except _lib.KmError as e:
                     raise _lib.KmError(e.code, "%s: %s" % (path, e.detail)) from e
                 finally:
-                    if close:
-                        fh.close()
+                    blocks.close()
             return sel.stats()
 
 
@@ -470,10 +453,7 @@ def write_records(path, keys, counts, k, canonical, cmdline=None):
     Real Jellyfish orders the records of such a file by its matrix hash and binary-searches that order; it
     could not query this file (write_jellyfish writes that order).  Readers that load all records (every reader
     here) do not care."""
-    keys = np.ascontiguousarray(keys, dtype=np.uint64)
-    counts = np.ascontiguousarray(counts, dtype=np.uint32)
-    if keys.shape != counts.shape or keys.ndim != 1:
-        raise ValueError("keys and counts must be 1-d arrays of one length")
+    keys, counts = _lib._records(keys, counts)
     if not 2 <= int(k) <= 32:
         raise ValueError("k=%d unsupported" % k)
     order = np.argsort(keys, kind="stable")
@@ -509,10 +489,7 @@ def write_jellyfish(path, keys, counts, k, canonical, cmdline=None, seed=0, devi
     matrix1 from `seed`, the keys of a real Jellyfish header minus the informational ones) comes from the
     library's own writer and the records are sorted on the GPU, so the file equals, byte for byte, what
     Counter.write_jf writes for the same records, cmdline and seed."""
-    keys = np.ascontiguousarray(keys, dtype=np.uint64)
-    counts = np.ascontiguousarray(counts, dtype=np.uint32)
-    if keys.shape != counts.shape or keys.ndim != 1:
-        raise ValueError("keys and counts must be 1-d arrays of one length")
+    keys, counts = _lib._records(keys, counts)
     if not 2 <= int(k) <= 32:
         raise ValueError("k=%d unsupported" % k)
     header, columns, size_log2 = _lib.jf_header(k, canonical, keys.size, cmdline=cmdline, seed=seed)

@@ -302,15 +302,23 @@ static int fastq_front(FastqDev& f, const uint8_t* d_text, uint64_t n, uint64_t 
   const uint32_t n_chunks = (uint32_t)(((uint64_t)n_tiles + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK);
   HIPCHK(hipMemsetAsync(f.tiles, 0, (uint64_t)n_chunks * SCAN_CHUNK * 4, st));
   hipLaunchKernelGGL(k_fq_count_lines, dim3(n_tiles), dim3(FQ_THREADS), 0, st, d_text, n, f.tiles.p);
-  hipLaunchKernelGGL(k_scan_reduce, dim3(n_chunks), dim3(SCAN_THREADS), 0, st, f.tiles.p, f.sums.p);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, st, f.sums.p, n_chunks);
-  hipLaunchKernelGGL(k_scan_apply, dim3(n_chunks), dim3(SCAN_THREADS), 0, st, f.tiles.p, f.sums.p);
+  scan_in_place(f.tiles.p, f.sums.p, n_chunks, st);
   hipLaunchKernelGGL(k_fq_line_starts, dim3(n_tiles), dim3(FQ_THREADS), 0, st, d_text, n, f.tiles.p, n_tiles,
                      f.line_start.p);
   hipLaunchKernelGGL(k_fq_mask, dim3(n_tiles), dim3(FQ_THREADS), 0, st, d_text, n, f.tiles.p, n_tiles,
                      f.line_start.p, min_qual, base, f.masked.p, error_cell);
   HIPCHK(hipGetLastError());
   if (tiles_out) *tiles_out = n_tiles;
+  return KM_OK;
+}
+
+// The next piece of text[pos .. end) for every caller that sends FASTQ pieces (kmcut::next_piece), or KM_E_CAPACITY:
+// a record longer than a staging buffer.  stream_offset: where text[0] lies in the stream.
+static int fastq_take(const char* text, uint64_t pos, uint64_t end, uint64_t stage, uint64_t stream_offset, uint64_t* take) {
+  *take = kmcut::next_piece(text, pos, end, stage);
+  if (*take == 0)
+    return fail(KM_E_CAPACITY, "no FASTQ record ends within the %llu bytes of a staging buffer from byte offset %llu",
+                (unsigned long long)stage, (unsigned long long)(stream_offset + pos));
   return KM_OK;
 }
 
@@ -340,7 +348,7 @@ extern "C" int km_counter_add_fastq(km_counter_t* c, const char* text, uint64_t 
   if (min_qual_char < 0 || min_qual_char > 255) return fail(KM_E_ARG, "min_qual_char %d outside 0..255", min_qual_char);
   KMCHK(counter_takes_plain(c));
   *consumed = 0;
-  const uint64_t end = final ? n : kmcut::cut(text, n);
+  const uint64_t end = kmcut::call_end(text, n, final);
   if (end) {
     HIPCHK(hipSetDevice(c->device));
     KMCHK(fastq_prepare(c));
@@ -348,13 +356,8 @@ extern "C" int km_counter_add_fastq(km_counter_t* c, const char* text, uint64_t 
     KMCHK(counter_begin_pieces(c));
   }
   for (uint64_t pos = 0; pos < end;) {
-    uint64_t take = end - pos;
-    if (take > c->stg.bytes) {
-      take = kmcut::cut(text + pos, c->stg.bytes);
-      if (take == 0)
-        return fail(KM_E_CAPACITY, "no FASTQ record ends within the %llu bytes of a staging buffer from byte offset %llu",
-                    (unsigned long long)c->stg.bytes, (unsigned long long)(c->fq_offset + pos));
-    }
+    uint64_t take = 0;
+    KMCHK(fastq_take(text, pos, end, c->stg.bytes, c->fq_offset, &take));
     KMCHK(fastq_enqueue(c, text + pos, take, c->fq_offset + pos, (uint32_t)min_qual_char));
     pos += take;
     *consumed = pos;

@@ -103,14 +103,21 @@ struct DumpRun {
 
 // The last leg of every call that writes device-made text to a descriptor (here and in select_host.h): per pinned
 // buffer of a Staging the bytes of the copy in flight into it; put() waits for that copy and writes them, short writes
-// and EINTR handled in dump_write_all, any other failure (EPIPE: the reader went away) is KM_E_IO.
+// and EINTR handled in dump_write_all, any other failure (EPIPE: the reader went away) is KM_E_IO.  The two buffers
+// take turns piece by piece: begin() hands out this piece's, put_before() writes the piece before it while this one is
+// made on the device, fetch() starts this piece's copy, and flush() ends a call.
 struct TextDrain {
   Staging* out = nullptr;
   hipStream_t cs = nullptr;               // the copy stream
   int fd = -1;
+  int turn = 0;                           // the buffer of the next piece
   uint64_t pending[2] = {0, 0};           // bytes of the copy in flight into out->pin[i]
   bool close_line[2] = {false, false};    // the text in out->pin[i] gets a newline behind it unless it ends in one
   uint64_t closed = 0;                    // (the buffers have a byte of padding for it) ... and how often that happened
+  int begin() {
+    turn ^= 1;
+    return turn ^ 1;
+  }
   // bytes of d_src (ready: the host has waited for what wrote them) on their way into out->pin[buf]
   int fetch(int buf, const void* d_src, uint64_t bytes) {
     if (bytes) KMCHK(out->fetch(buf, d_src, bytes, cs));
@@ -131,6 +138,16 @@ struct TextDrain {
     if (const int e = dump_write_all(fd, got, n)) return fail(KM_E_IO, "writing the text failed: %s", strerror(e));
     return KM_OK;
   }
+  int put_before(int buf) { return put(buf ^ 1); }
+  // What is still on its way is written, the older of the two first; the newlines that closed a last line count as
+  // bytes of the caller's.
+  int flush(uint64_t* bytes_out) {
+    int rc = put(turn);
+    if (rc == KM_OK) rc = put(turn ^ 1);
+    *bytes_out += closed;
+    closed = 0;
+    return rc;
+  }
 };
 
 // The way out of the calls that write records as text: piece after piece, formatted on `st` into the text buffer
@@ -139,19 +156,19 @@ struct DumpPipe : TextDrain {
   DumpRun run;
   hipStream_t st = nullptr;
   km_dump_stats_t stats;
-  int turn = 0;
+  StreamDrain sync;                       // (last: both streams are waited for before the tables and texts of `run` go)
   DumpPipe() { memset(&stats, 0, sizeof stats); }
-  // never leaves a copy into a freed buffer, or a kernel on a freed table, in flight
-  ~DumpPipe() {
-    if (st) (void)hipStreamSynchronize(st);
-    if (cs) (void)hipStreamSynchronize(cs);
+  void open(Staging* text_out, hipStream_t launch, hipStream_t copy, int out_fd) {
+    out = text_out;
+    st = sync.st = launch;
+    cs = sync.cs = copy;
+    fd = out_fd;
   }
   template <typename Src>
   int piece(const Src& src, uint64_t n) {
-    const int buf = turn;
-    turn ^= 1;
+    const int buf = begin();
     KMCHK(run.format(src, n, buf, true, st));
-    KMCHK(put(buf ^ 1));                  // the piece before, while this one is formatted
+    KMCHK(put_before(buf));               // while this one is formatted
     uint64_t bytes = 0, kept = 0;
     KMCHK(run.wait(buf, &bytes, &kept));
     stats.records_in += n;
@@ -161,8 +178,7 @@ struct DumpPipe : TextDrain {
     return fetch(buf, run.text[buf].p, bytes);
   }
   int finish(km_dump_stats_t* to) {
-    KMCHK(put(turn));                     // (the older of the two first)
-    KMCHK(put(turn ^ 1));
+    KMCHK(flush(&stats.bytes_out));       // (adds nothing: no piece of records leaves a line open)
     HIPCHK(hipStreamSynchronize(st));
     KMCHK(run.spans.drain(&g_dump_kernel_ms));
     if (to) *to = stats;
@@ -191,17 +207,13 @@ extern "C" int km_dump_text(int device, const uint64_t* keys, const uint32_t* co
   const uint64_t per = dump_text_records(sized.bytes, k);
   CallStream st;
   KMCHK(st.get(device, stream));
-  struct Drain {
-    hipStream_t st;
-    ~Drain() { (void)hipStreamSynchronize(st); }
-  };
   DevBuf<uint64_t> d_keys;
   DevBuf<uint32_t> d_counts;
   DumpRun run;
   KMCHK(d_keys.alloc(n));
   KMCHK(d_counts.alloc(n));
   KMCHK(run.begin(rule, sized.bytes, 1));
-  Drain drain{st};
+  StreamDrain drain{st};
   HIPCHK(hipMemcpyAsync(d_keys, keys, n * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_counts, counts, n * 4, hipMemcpyHostToDevice, st));
   // first the length of the whole text, so that a buffer too small is left untouched; then the text
@@ -259,11 +271,8 @@ extern "C" int km_jf_dump(int device, const char* path, int out_fd, int format, 
   KMCHK(out.alloc(0));
   KMCHK(d_raw.alloc(in.bytes));
   DumpPipe pipe;                                        // (after the buffers: its destructor drains both streams first)
+  pipe.open(&out, st, cs, out_fd);
   KMCHK(pipe.run.begin(DumpRule{k, format, lower, upper}, out.bytes, 2));
-  pipe.out = &out;
-  pipe.st = st;
-  pipe.cs = cs;
-  pipe.fd = out_fd;
   const uint64_t pieces = kmpiece::n_pieces(n, per);
   for (uint64_t i = 0; i < pieces; ++i) {
     const kmpiece::Piece p = kmpiece::piece(n, per, rec, i);
@@ -289,11 +298,8 @@ extern "C" int km_counter_dump(km_counter_t* c, int out_fd, int format, uint32_t
   CallStream cs;
   KMCHK(cs.get(c->device, nullptr));
   DumpPipe pipe;
+  pipe.open(&c->stg, c->st, cs, out_fd);                // (idle once the counter has finished, as for write_jf)
   KMCHK(pipe.run.begin(DumpRule{c->k, format, lower, upper}, c->stg.bytes, 2));
-  pipe.out = &c->stg;                                   // idle once the counter has finished, as for write_jf
-  pipe.st = c->st;
-  pipe.cs = cs;
-  pipe.fd = out_fd;
   for (uint64_t first = 0; first < n; first += per)     // T^32 of a non-canonical k = 32 table is among the records
     KMCHK(pipe.piece(DumpArrays{c->out_keys.p + first, c->out_counts.p + first}, std::min(per, n - first)));
   return pipe.finish(stats);
@@ -319,11 +325,8 @@ extern "C" int kmjf_query_text(kmjf_t* h, const uint64_t* kmers, uint64_t n, int
   KMCHK(d_kmers.alloc(per));
   KMCHK(d_counts.alloc(per));
   DumpPipe pipe;
+  pipe.open(&out, st, cs, out_fd);
   KMCHK(pipe.run.begin(DumpRule{h->k, KM_DUMP_COLUMN, 0u, 0xFFFFFFFFu}, out.bytes, 2));   // no filter: a 0 is printed
-  pipe.out = &out;
-  pipe.st = st;
-  pipe.cs = cs;
-  pipe.fd = out_fd;
   for (uint64_t first = 0; first < n; first += per) {
     const uint64_t m = std::min(per, n - first);
     KMCHK(in.claim());

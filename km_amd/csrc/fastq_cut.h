@@ -37,4 +37,15 @@ inline uint64_t cut(const char* text, uint64_t n) {
   return 0;
 }
 
+// ---- the pieces of a call: what every consumer of raw FASTQ text (counter, selector, pair selector, kmjf_fastq_hits)
+// sends to the device, one staging buffer at a time
+// The end of what a call may take of text[0 .. n): all of it when the stream ends with the call, else its whole records.
+inline uint64_t call_end(const char* text, uint64_t n, bool final) { return final ? n : cut(text, n); }
+
+// The next piece of text[pos .. end), pos < end, for staging buffers of `stage` bytes: all that is left if that fits,
+// else the whole records within the next `stage` bytes; 0: no record ends within them.
+inline uint64_t next_piece(const char* text, uint64_t pos, uint64_t end, uint64_t stage) {
+  return end - pos <= stage ? end - pos : cut(text + pos, stage);
+}
+
 }  // namespace kmcut

@@ -1,4 +1,4 @@
-// host_common.h — what every host part of kmgpu.hip shares: error plumbing, owned resources, Staging, the stream pool
+// host_common.h — what every host part of kmgpu.hip shares: error plumbing, the in-place scan, owned resources, Staging, the stream pool
 // ------------------------------------------------------------------ error plumbing
 static thread_local std::string g_last_error;
 
@@ -56,6 +56,14 @@ static int grid_for(uint64_t n, int block) {
 
 static double host_now_us() {
   return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// The scan of table_kernels.h: data[0 .. chunks * SCAN_CHUNK) becomes its exclusive prefix sums on `stream`, sums[0 ..
+// chunks) is its scratch.  (Launches only: the caller asks hipGetLastError with its own.)
+static void scan_in_place(uint32_t* data, uint32_t* sums, uint32_t chunks, hipStream_t stream) {
+  hipLaunchKernelGGL(k_scan_reduce, dim3(chunks), dim3(SCAN_THREADS), 0, stream, data, sums);
+  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, stream, sums, chunks);
+  hipLaunchKernelGGL(k_scan_apply, dim3(chunks), dim3(SCAN_THREADS), 0, stream, data, sums);
 }
 
 // ------------------------------------------------------------------ owned resources
@@ -261,6 +269,19 @@ struct CallStream {
     st = (hipStream_t)stream;
     if (!st) { KMCHK(pool_get(device, &st)); own = true; }
     return KM_OK;
+  }
+};
+
+// Declared after what its streams (a launch stream; a copy stream, if there is one) work on, in a call or in an owner:
+// waits for both before any of that is freed, so no copy into a freed buffer and no kernel on one stays in flight.
+// device >= 0: made current first (an owner that may go on another thread than the one that made it).
+struct StreamDrain {
+  hipStream_t st = nullptr, cs = nullptr;
+  int device = -1;
+  ~StreamDrain() {
+    if (device >= 0) (void)hipSetDevice(device);
+    if (st) (void)hipStreamSynchronize(st);
+    if (cs) (void)hipStreamSynchronize(cs);
   }
 };
 }  // namespace

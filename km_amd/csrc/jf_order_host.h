@@ -70,9 +70,7 @@ int jf_sort_device(const uint64_t* columns, int k, int size_log2, const uint64_t
   const int grid = grid_for(n, JF_THREADS);
   hipLaunchKernelGGL(k_jf_position, dim3(grid), dim3(JF_THREADS), 0, st, d_cols.p, c, mask, d_keys, n, pos.p, dir.p,
                      shift, bits);
-  hipLaunchKernelGGL(k_scan_reduce, dim3(n_chunks), dim3(SCAN_THREADS), 0, st, dir.p, sums.p);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, st, sums.p, n_chunks);
-  hipLaunchKernelGGL(k_scan_apply, dim3(n_chunks), dim3(SCAN_THREADS), 0, st, dir.p, sums.p);
+  scan_in_place(dir.p, sums.p, n_chunks, st);
   hipLaunchKernelGGL(k_jf_bucket_stats, dim3(grid_for(n_buckets, 256)), dim3(256), 0, st, dir.p, n_buckets, d_stats.p);
   hipLaunchKernelGGL(k_jf_scatter, dim3(grid), dim3(JF_THREADS), 0, st, pos.p, d_keys, d_counts, n, dir.p, cursor.p,
                      shift, bits, pos2.p, keys2.p, counts2.p);

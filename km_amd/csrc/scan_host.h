@@ -8,11 +8,6 @@
 namespace {
 thread_local float g_scan_kernel_ms = 0.f;
 
-struct StreamDrain {                      // declared after what the stream works on: waits before any of it is freed
-  hipStream_t st;
-  ~StreamDrain() { (void)hipStreamSynchronize(st); }
-};
-
 // What both calls check alike, in this order.  *total: the bytes of all sequences.
 int scan_check(const kmjf* h, const uint8_t* text, const uint64_t* seq_off, uint64_t n_seqs, uint64_t* total) {
   if (!h->d_slots) return fail(KM_E_STATE, "table not uploaded");
@@ -151,11 +146,8 @@ extern "C" int kmjf_scan_text(kmjf_t* h, const uint8_t* text, const uint64_t* se
   KMCHK(d_counts.alloc(per));
   KMCHK(d_lines.alloc((per + kmscan::RUN - 1) / kmscan::RUN));
   DumpPipe pipe;                                        // (after the buffers: its destructor drains both streams first)
-  pipe.st = st;
-  pipe.cs = cs;
+  pipe.open(&out, st, cs, out_fd);
   KMCHK(pipe.run.begin(DumpRule{h->k, KM_DUMP_COLUMN, 0u, 0xFFFFFFFFu}, out.bytes, 2));   // no filter: a 0 is printed
-  pipe.out = &out;
-  pipe.fd = out_fd;
   KMCHK(run.send_offsets(st));
   const TableView tv = view_of(h);
   const uint64_t begin = seq_off[0], end = seq_off[n_seqs];

@@ -62,9 +62,7 @@ struct SelDev {
     KMCHK(spans[2].open(st));
     hipLaunchKernelGGL(k_sel_sizes, dim3(chunks * (SCAN_CHUNK / kmsel::THREADS)), dim3(kmsel::THREADS), 0, st,
                        fq.line_start.p, (uint32_t)n, hits.p, min_hits, invert ? 1u : 0u, len.p, cells());
-    hipLaunchKernelGGL(k_scan_reduce, dim3(chunks), dim3(SCAN_THREADS), 0, st, len.p, sums.p);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, st, sums.p, chunks);
-    hipLaunchKernelGGL(k_scan_apply, dim3(chunks), dim3(SCAN_THREADS), 0, st, len.p, sums.p);
+    scan_in_place(len.p, sums.p, chunks, st);
     HIPCHK(hipGetLastError());
     KMCHK(spans[2].close(st));
     KMCHK(spans[3].open(st));
@@ -97,45 +95,76 @@ int select_check_qual(int min_qual_char) {
   return KM_OK;
 }
 
-// the next piece of text[pos .. end): everything, or the whole records within a staging buffer
-int select_take(const char* text, uint64_t pos, uint64_t end, uint64_t stage, uint64_t stream_offset, uint64_t* take) {
-  *take = end - pos;
-  if (*take > stage) {
-    *take = kmcut::cut(text + pos, stage);
-    if (*take == 0)
-      return fail(KM_E_CAPACITY, "no FASTQ record ends within the %llu bytes of a staging buffer from byte offset %llu",
-                  (unsigned long long)stage, (unsigned long long)(stream_offset + pos));
-  }
+// What km_select_create and km_select_pair_create check of their arguments, in this order.  The single selector is the
+// rule "any" (0) over one descriptor.
+int select_check_create(const kmjf* h, const void* out, uint32_t min_hits, int min_qual_char, int rule, const int* fds,
+                        int n_fds) {
+  if (!h || !out) return fail(KM_E_ARG, "null argument");
+  if (min_hits == 0) return fail(KM_E_ARG, "min_hits must be at least 1");
+  KMCHK(select_check_qual(min_qual_char));
+  if (rule < 0 || rule >= (int)kmpair::RULE_COUNT) return fail(KM_E_ARG, "pair rule %d is none of any (0), both (1), sum (2)", rule);
+  if (n_fds == 2 && fds[0] == fds[1]) return fail(KM_E_ARG, "the two mates need two descriptors, both are %d", fds[0]);
+  if (!h->d_slots) return fail(KM_E_STATE, "table not uploaded");
+  for (int i = 0; i < n_fds; ++i) KMCHK(dump_check_fd(fds[i]));
   return KM_OK;
 }
-}  // namespace
 
-struct km_select {
+// What km_select and km_select_pair share: the table and the numbers of the rule, the two streams with the events of
+// the two output buffers, and the end of a call.  The owner declares it first (the streams are released last) and a
+// StreamDrain last (both are waited for before any buffer goes).
+struct SelCore {
   kmjf_t* h = nullptr;
   uint32_t min_hits = 1, min_qual = 0;
   int invert = 0;
-  CallStream st, cs;                      // (declared before what runs on them: released after it)
+  CallStream st, cs;                      // launch and copy
+  Event done[2];                          // the piece gathered into output buffer i is done, its totals are there
+  int dead = KM_OK;                       // the code a call failed with: every further call fails the same way
+  std::string dead_msg;
+  int open(kmjf_t* table, uint32_t hits, int inv, int min_qual_char, void* stream, StreamDrain* sync) {
+    h = table;
+    min_hits = hits;
+    invert = inv ? 1 : 0;
+    min_qual = (uint32_t)min_qual_char;
+    KMCHK(st.get(h->device, stream));
+    KMCHK(cs.get(h->device, nullptr));
+    sync->st = st;
+    sync->cs = cs;
+    sync->device = h->device;
+    for (Event& e : done) HIPCHK(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+    return KM_OK;
+  }
+  int alive() const { return dead == KM_OK ? KM_OK : fail(dead, "%s", dead_msg.c_str()); }
+  // The end of every add_fastq: rc and msg are what the pieces came to, rc_flush what writing the text they kept came
+  // to (the flush comes whatever rc is: what the pieces before a failure kept is written).  Whatever failed, nothing
+  // stays in flight and the selector fails from now on: its offsets and the descriptor's content no longer match what
+  // a caller who went on would assume.
+  int end_call(int rc, std::string msg, int rc_flush) {
+    if (rc == KM_OK && rc_flush != KM_OK) {
+      rc = rc_flush;
+      msg = g_last_error;
+    }
+    if (rc == KM_OK) return KM_OK;
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamSynchronize(cs);
+    dead = rc;
+    dead_msg = msg;
+    return fail(rc, "%s", msg.c_str());
+  }
+};
+}  // namespace
+
+struct km_select : SelCore {
   Staging in, out;
   SelDev dev;
   DevBuf<uint8_t> d_out[2];
-  Event done[2];                          // the piece gathered into d_out[i] is done, its totals are there
   TextDrain drain;
-  int turn = 0;
   uint64_t offset = 0;                    // bytes consumed by the earlier calls of this stream
-  int dead = KM_OK;                       // the code a call failed with: every further call fails the same way
-  std::string dead_msg;
   km_select_stats_t stats;
+  StreamDrain sync;
   km_select() { memset(&stats, 0, sizeof stats); }
-  // never leaves a copy into a freed buffer, or a kernel on a freed one, in flight
-  ~km_select() {
-    if (h) (void)hipSetDevice(h->device);
-    if (st.st) (void)hipStreamSynchronize(st);
-    if (cs.st) (void)hipStreamSynchronize(cs);
-  }
   // One piece of whole records; ends: the stream ends with it.
   int piece(const char* text, uint64_t n, uint64_t base, bool ends) {
-    const int buf = turn;
-    turn ^= 1;
+    const int buf = drain.begin();
     KMCHK(in.claim());
     memcpy(in.mine, text, n);
     KMCHK(in.ship(dev.d_text, n, st));
@@ -143,7 +172,7 @@ struct km_select {
     KMCHK(dev.gather(n, min_hits, invert, d_out[buf].p, st));
     KMCHK(dev.read_back(buf, st));
     HIPCHK(hipEventRecord(done[buf], st));
-    KMCHK(drain.put(buf ^ 1));            // the piece before, while this one is scanned
+    KMCHK(drain.put_before(buf));         // while this one is scanned
     HIPCHK(hipEventSynchronize(done[buf]));
     KMCHK(dev.drain_spans());
     if (dev.error_of(buf) != FQ_NO_ERROR) return select_format_failed(dev.error_of(buf));
@@ -156,13 +185,7 @@ struct km_select {
     drain.close_line[buf] = ends && text[n - 1] != '\n';
     return drain.fetch(buf, d_out[buf].p, c[SEL_BYTES]);
   }
-  int flush() {
-    KMCHK(drain.put(turn));               // (the older of the two first)
-    KMCHK(drain.put(turn ^ 1));
-    stats.bytes_out += drain.closed;
-    drain.closed = 0;
-    return KM_OK;
-  }
+  int flush() { return drain.flush(&stats.bytes_out); }
 };
 
 extern "C" int km_select_kernel_ms(float* ms) {
@@ -173,26 +196,14 @@ extern "C" int km_select_kernel_ms(float* ms) {
 
 extern "C" int km_select_create(kmjf_t* h, uint32_t min_hits, int invert, int min_qual_char, int out_fd, void* stream,
                                 km_select_t** out) {
-  if (!h || !out) return fail(KM_E_ARG, "null argument");
-  if (min_hits == 0) return fail(KM_E_ARG, "min_hits must be at least 1");
-  KMCHK(select_check_qual(min_qual_char));
-  if (!h->d_slots) return fail(KM_E_STATE, "table not uploaded");
-  KMCHK(dump_check_fd(out_fd));
+  KMCHK(select_check_create(h, out, min_hits, min_qual_char, 0, &out_fd, 1));
   std::unique_ptr<km_select> s(new (std::nothrow) km_select);
   if (!s) return fail(KM_E_NOMEM, "host allocation failed");
-  s->h = h;
-  s->min_hits = min_hits;
-  s->invert = invert ? 1 : 0;
-  s->min_qual = (uint32_t)min_qual_char;
-  KMCHK(s->st.get(h->device, stream));
-  KMCHK(s->cs.get(h->device, nullptr));
+  KMCHK(s->open(h, min_hits, invert, min_qual_char, stream, &s->sync));
   KMCHK(s->in.alloc(0));
   KMCHK(s->out.alloc(1));                               // (room for the newline behind an open last line)
   KMCHK(s->dev.alloc(s->in.bytes, true, s->st));
-  for (int i = 0; i < 2; ++i) {
-    KMCHK(s->d_out[i].alloc(s->in.bytes + kmsel::OUT_PAD));
-    HIPCHK(hipEventCreateWithFlags(&s->done[i].h, hipEventDisableTiming));
-  }
+  for (int i = 0; i < 2; ++i) KMCHK(s->d_out[i].alloc(s->in.bytes + kmsel::OUT_PAD));
   HIPCHK(hipStreamSynchronize(s->st));
   s->drain.out = &s->out;
   s->drain.cs = s->cs;
@@ -204,37 +215,26 @@ extern "C" int km_select_create(kmjf_t* h, uint32_t min_hits, int invert, int mi
 
 extern "C" int km_select_add_fastq(km_select_t* s, const char* text, uint64_t n, int final, uint64_t* consumed) {
   if (!s || !consumed || (n && !text)) return fail(KM_E_ARG, "null argument");
-  if (s->dead != KM_OK) return fail(s->dead, "%s", s->dead_msg.c_str());
+  KMCHK(s->alive());
   *consumed = 0;
   if (n == 0) {                                         // nothing for the device or the descriptor; an empty final
     if (final) s->offset = 0;                           // call still ends the stream: the next one's offsets start at 0
     return KM_OK;
   }
-  const uint64_t end = final ? n : kmcut::cut(text, n);
+  const uint64_t end = kmcut::call_end(text, n, final);
   if (end) HIPCHK(hipSetDevice(s->h->device));
   int rc = KM_OK;
   for (uint64_t pos = 0; pos < end && rc == KM_OK;) {
     uint64_t take = 0;
-    rc = select_take(text, pos, end, s->in.bytes, s->offset, &take);
+    rc = fastq_take(text, pos, end, s->in.bytes, s->offset, &take);
     if (rc == KM_OK) rc = s->piece(text + pos, take, s->offset + pos, final && pos + take == end);
     if (rc == KM_OK) {
       pos += take;
       *consumed = pos;
     }
   }
-  std::string msg = rc != KM_OK ? g_last_error : std::string();
-  const int rc_flush = s->flush();                      // what the pieces before a failure kept is written
-  if (rc == KM_OK && rc_flush != KM_OK) {
-    rc = rc_flush;
-    msg = g_last_error;
-  }
-  if (rc != KM_OK) {                                    // whatever failed: nothing stays in flight, and the selector
-    (void)hipStreamSynchronize(s->st);                  // fails from now on (its offsets and the descriptor's content
-    (void)hipStreamSynchronize(s->cs);                  // no longer match what a caller who went on would assume)
-    s->dead = rc;
-    s->dead_msg = msg;
-    return fail(rc, "%s", msg.c_str());
-  }
+  const std::string msg = rc != KM_OK ? g_last_error : std::string();
+  KMCHK(s->end_call(rc, msg, s->flush()));
   s->offset = final ? 0 : s->offset + end;
   return KM_OK;
 }
@@ -269,7 +269,7 @@ extern "C" int kmjf_fastq_hits(kmjf_t* h, const char* text, uint64_t n, int min_
   uint64_t done = 0;
   for (uint64_t pos = 0; pos < n;) {
     uint64_t take = 0;
-    KMCHK(select_take(text, pos, n, in.bytes, 0, &take));
+    KMCHK(fastq_take(text, pos, n, in.bytes, 0, &take));
     KMCHK(in.claim());
     memcpy(in.mine, text + pos, take);
     KMCHK(in.ship(dev.d_text, take, st));

@@ -156,21 +156,50 @@ _LIVE_DATABASES = weakref.WeakSet()
 
 
 def close_all_handles():
-    for c in list(_LIVE_COUNTERS):
+    for live in (_LIVE_COUNTERS, _LIVE_BATCHES, _LIVE_DATABASES):
+        for handle in list(live):
+            try:
+                handle.close()
+            except Exception:
+                pass
+
+
+class _Handle:
+    """The life of one native handle, for every class that owns one: `_slot` names the attribute that holds it (a
+    c_void_p; None once closed), `_destroy` the library call that frees it and `_live` the set close_all_handles walks.
+    A subclass sets self._lib and the slot, makes the handle and calls _opened(); close() is safe to repeat, and runs
+    from a `with` block, from the collector and at interpreter exit."""
+    _slot = _destroy = _live = None
+
+    def _opened(self):
+        self._live.add(self)
+
+    def close(self):
+        h = getattr(self, self._slot, None)
+        if h is not None and h.value:
+            getattr(self._lib, self._destroy)(h)
+        setattr(self, self._slot, None)
+
+    def __del__(self):
         try:
-            c.close()
+            self.close()
         except Exception:
             pass
-    for b in list(_LIVE_BATCHES):
-        try:
-            b.close()
-        except Exception:
-            pass
-    for d in list(_LIVE_DATABASES):
-        try:
-            d.close()
-        except Exception:
-            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _records(keys, counts):
+    """(keys, counts) as the contiguous uint64 / uint32 arrays the library takes, 1-d and of one length."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if keys.shape != counts.shape or keys.ndim != 1:
+        raise ValueError("keys and counts must be 1-d arrays of one length")
+    return keys, counts
 
 
 atexit.register(close_all_handles)
@@ -392,15 +421,16 @@ def typed_ptr(arr, ctype):
     return None if arr is None else arr.ctypes.data_as(C.POINTER(ctype))
 
 
-class Database:
+class Database(_Handle):
     """One k-mer count database: host records + HBM-resident table.
 
     Replaces the ``QueryMerFile`` handle of km/utils/Jellyfish.py:24."""
+    _slot, _destroy, _live = "_h", "kmjf_close", _LIVE_DATABASES
 
     def __init__(self, handle):
         self._h = handle
         self._lib = load()
-        _LIVE_DATABASES.add(self)
+        self._opened()
 
     @classmethod
     def open(cls, path):
@@ -434,17 +464,6 @@ class Database:
         h = C.c_void_p()
         check(lib.kmjf_create(int(k), int(bool(canonical)), C.byref(h)))
         return cls(h)
-
-    def close(self):
-        if self._h is not None:
-            self._lib.kmjf_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def info(self):
@@ -604,10 +623,11 @@ def _qual_byte(min_qual_char):
     return int(min_qual_char)
 
 
-class Counter:
+class Counter(_Handle):
     """k-mers counted from reads on the GPU (km_counter_*, include/kmgpu.h): what `jellyfish count -m k [-C]
     -s expected_distinct` does.  add_bases / add_text / add_fastq feed it, finish() hands back a Database whose table was
     built on the device from the counted records."""
+    _slot, _destroy, _live = "_c", "km_counter_destroy", _LIVE_COUNTERS
 
     def __init__(self, k=31, canonical=True, device=0, expected_distinct=0):
         self._lib = load()
@@ -615,18 +635,7 @@ class Counter:
         self.k, self.canonical, self.device = int(k), bool(canonical), int(device)
         check(self._lib.km_counter_create(self.device, self.k, int(self.canonical), int(expected_distinct),
                                           C.byref(self._c)))
-        _LIVE_COUNTERS.add(self)
-
-    def close(self):
-        if self._c is not None and self._c.value:
-            self._lib.km_counter_destroy(self._c)
-        self._c = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._opened()
 
     def add_bases(self, data):
         """Bases (ACGTacgt) and breaks (any other byte); k-mers never span two calls."""
@@ -662,10 +671,7 @@ class Counter:
     def add_records(self, keys, counts, mode="sum"):
         """km_counter_add_records: (key, count) pairs into the table, per key summed (saturating at 2^32 - 1) or
         the maximum kept (mode "sum" / "max"); pairs with count 0 are skipped, keys may repeat."""
-        keys = np.ascontiguousarray(keys, dtype=np.uint64)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        if keys.shape != counts.shape or keys.ndim != 1:
-            raise ValueError("keys and counts must be 1-d arrays of one length")
+        keys, counts = _records(keys, counts)
         check(self._lib.km_counter_add_records(self._c, ptr(keys) if keys.size else None,
                                                ptr(counts) if counts.size else None, keys.size, _merge_mode(mode)))
 
@@ -681,10 +687,7 @@ class Counter:
         "intersect": the keys with count > 0 in every input, with the minimum over all their records; "subtract": the
         records of the first input whose key is, with count > 0, in no later one.  Pairs with count 0 are absent, keys
         may repeat (one input all the same), an empty call is an empty input.  This project's own definitions."""
-        keys = np.ascontiguousarray(keys, dtype=np.uint64)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        if keys.shape != counts.shape or keys.ndim != 1:
-            raise ValueError("keys and counts must be 1-d arrays of one length")
+        keys, counts = _records(keys, counts)
         check(self._lib.km_counter_set_records(self._c, ptr(keys) if keys.size else None,
                                                ptr(counts) if counts.size else None, keys.size, _set_op(op)))
 
@@ -847,10 +850,7 @@ def dump_text(keys, counts, k, fmt="fasta", lower_count=0, upper_count=0xFFFFFFF
     """km_dump_text: the records (keys, counts) with lower_count <= count <= upper_count as the text of `dump`, in
     the order given -> bytes.  fmt "fasta" is ">COUNT\nMER\n", "column" "MER COUNT\n", "tab" "MER\tCOUNT\n"
     (include/kmgpu.h has the rule: this project's reading of `jellyfish dump`)."""
-    keys = np.ascontiguousarray(keys, dtype=np.uint64)
-    counts = np.ascontiguousarray(counts, dtype=np.uint32)
-    if keys.shape != counts.shape or keys.ndim != 1:
-        raise ValueError("keys and counts must be 1-d arrays of one length")
+    keys, counts = _records(keys, counts)
     out = np.empty(max(keys.size * (max(int(k), 0) + 13), 1), np.uint8)          # the longest line is k + 13 bytes
     ln = C.c_uint64()
     check(load().km_dump_text(int(device), ptr(keys) if keys.size else None, ptr(counts) if counts.size else None,
@@ -884,11 +884,12 @@ def scan_kernel_ms():
     return float(ms.value)
 
 
-class Selector:
+class Selector(_Handle):
     """The FASTQ reads that hit a table, extracted on the GPU (km_select_*, include/kmgpu.h): a read is kept iff
     (its windows of k bases with a count > 0 in `db` number at least min_hits) != invert, and the kept records go to
     `out` (a descriptor, or a file object with fileno()) byte for byte, in input order.  `db` must stay open for as long
     as the selector lives.  A context manager; close() releases the device side."""
+    _slot, _destroy, _live = "_s", "km_select_destroy", _LIVE_COUNTERS
 
     def __init__(self, db, out, min_hits=1, invert=False, min_qual_char=None, stream=None):
         self._lib = load()
@@ -896,24 +897,7 @@ class Selector:
         self._db = db
         check(self._lib.km_select_create(db._h, int(min_hits), int(bool(invert)), _qual_byte(min_qual_char or 0),
                                          out_descriptor(out), C.c_void_p(stream or 0), C.byref(self._s)))
-        _LIVE_COUNTERS.add(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if self._s is not None and self._s.value:
-            self._lib.km_select_destroy(self._s)
-        self._s = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._opened()
 
     def add_fastq(self, data, final=False):
         """4-line FASTQ text; returns how many bytes were taken (whole records): pass the rest again in front of the
@@ -943,13 +927,14 @@ def select_kernel_ms():
 PAIR_RULES = {"any": 0, "both": 1, "sum": 2}     # KM_PAIR_ANY, KM_PAIR_BOTH, KM_PAIR_SUM
 
 
-class PairSelector:
+class PairSelector(_Handle):
     """The mates of a paired-end run that hit a table, kept together on the GPU (km_select_pair_*, include/kmgpu.h):
     record r of `data1` and record r of `data2` are pair r, kept iff (score >= min_hits) != invert with score =
     max(h1, h2) for rule "any", min(h1, h2) for "both" and h1 + h2 for "sum"; mate 1's kept records go to `out1` and
     mate 2's to `out2` (descriptors, or file objects with fileno()) byte for byte and in input order.  With check_names
     the mates' names (without a "/1" or "/2" at the end) must agree.  `db` must stay open for as long as the selector
     lives.  A context manager; close() releases the device side."""
+    _slot, _destroy, _live = "_s", "km_select_pair_destroy", _LIVE_COUNTERS
 
     def __init__(self, db, out1, out2, min_hits=1, invert=False, min_qual_char=None, rule="any", check_names=True,
                  stream=None):
@@ -962,24 +947,7 @@ class PairSelector:
         check(self._lib.km_select_pair_create(db._h, int(min_hits), int(bool(invert)), _qual_byte(min_qual_char or 0),
                                               code, int(bool(check_names)), out_descriptor(out1), out_descriptor(out2),
                                               C.c_void_p(stream or 0), C.byref(self._s)))
-        _LIVE_COUNTERS.add(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if self._s is not None and self._s.value:
-            self._lib.km_select_pair_destroy(self._s)
-        self._s = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._opened()
 
     def add_fastq(self, data1, data2, final=False):
         """4-line FASTQ text of mate 1 and of mate 2; returns (used1, used2), how many bytes of either were taken (whole
@@ -1055,10 +1023,7 @@ def jf_sort_records(columns, k, size_log2, keys, counts, device=0, want_pos=Fals
     """km_jf_sort_records: the file records (uint8[n, ceil(2k/8) + 4]) of (keys, counts) in (pos, key) order under
     the matrix `columns` (2k words, r = size_log2 rows), sorted on the GPU; with want_pos also their positions."""
     columns = np.ascontiguousarray(columns, dtype=np.uint64)
-    keys = np.ascontiguousarray(keys, dtype=np.uint64)
-    counts = np.ascontiguousarray(counts, dtype=np.uint32)
-    if keys.shape != counts.shape or keys.ndim != 1:
-        raise ValueError("keys and counts must be 1-d arrays of one length")
+    keys, counts = _records(keys, counts)
     if 2 <= int(k) <= 32 and columns.size != 2 * int(k):
         raise ValueError("%d columns for k=%d" % (columns.size, k))
     rec = (2 * int(k) + 7) // 8 + 4
@@ -1078,8 +1043,9 @@ def jf_sort_stats():
     return {"buckets": int(v[0]), "largest": int(v[1]), "oversized": int(v[2]), "kernel_ms": float(ms.value)}
 
 
-class Batch:
+class Batch(_Handle):
     """Device workspace that walks + path-searches many targets per launch."""
+    _slot, _destroy, _live = "_b", "km_batch_destroy", _LIVE_BATCHES
 
     def __init__(self, db, ratio=0.05, count=5, max_stack=500, max_break=10, max_node=10000,
                  max_targets=1024, max_total_bases=1 << 20):
@@ -1091,18 +1057,7 @@ class Batch:
         check(self._lib.km_batch_create(db._h, C.byref(self.params), int(max_targets),
                                         int(max_total_bases), C.byref(self._b)))
         self.n_targets = 0
-        _LIVE_BATCHES.add(self)
-
-    def close(self):
-        if self._b is not None and self._b.value:
-            self._lib.km_batch_destroy(self._b)
-            self._b = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._opened()
 
     def set_targets(self, seqs):
         """seqs: list of str/bytes (ACGT)."""

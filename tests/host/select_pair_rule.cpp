@@ -1,8 +1,8 @@
 // select_pair_rule.cpp — km_amd/csrc/select_pair_rule.h on the CPU (built with AddressSanitizer + UBSan by
 // tests/test_select_pair_cpu.py): two FASTQ texts (mate 1, mate 2) and a table come in as a file; for each given staging
 // size the two texts go the way km_select_pair_add_fastq sends two final streams: a piece of whole records from each
-// (kmcut::cut), per mate a line table, a masked copy and every lane's hit walk as tests/host/select_rule.cpp makes them,
-// then for R = min(records 1, records 2) the pair's lengths (kmpair::pair_lens), the name comparison
+// (kmcut::next_piece), per mate a line table, a masked copy and every lane's hit walk as tests/host/select_rule.cpp makes
+// them, then for R = min(records 1, records 2) the pair's lengths (kmpair::pair_lens), the name comparison
 // (kmpair::names_agree), the two scans, every word of both gathers (kmsel::gather_word with R, not the piece's own record
 // count) and the consumed offsets (kmpair::consumed), by which either stream advances: the surplus records of the longer
 // side are sent again with the next piece.  Every array has exactly the size of its device buffer, reads and writes go
@@ -167,12 +167,8 @@ int main(int argc, char** argv) {
     while (pos[0] < len[0] && pos[1] < len[1]) {
       uint32_t take[2];
       for (int m = 0; m < 2; ++m) {
-        uint64_t t = len[m] - pos[m];
-        if (t > stage) {
-          t = kmcut::cut(all[m].data() + pos[m], stage);
-          if (t == 0) die("no record ends within a staging buffer");
-        }
-        take[m] = (uint32_t)t;
+        take[m] = (uint32_t)kmcut::next_piece(all[m].data(), pos[m], len[m], stage);
+        if (take[m] == 0) die("no record ends within a staging buffer");
       }
       ++pieces;
       Side a(stage, all[0].data() + pos[0], take[0]), b(stage, all[1].data() + pos[1], take[1]);

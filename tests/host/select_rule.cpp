@@ -1,6 +1,6 @@
 // select_rule.cpp — km_amd/csrc/select_rule.h on the CPU (built with AddressSanitizer + UBSan by
 // tests/test_select_cpu.py): a FASTQ text and a table come in as a file; for each given staging size the text is cut into
-// pieces of whole records as the library cuts a final stream (kmcut::cut), and every piece goes the way it goes on the
+// pieces of whole records by the library's own cutter (kmcut::next_piece), and every piece goes the way it goes on the
 // device: a line table and a masked copy (made here from the rule of fastq_kernel.h's header comment, byte by byte),
 // then every lane's hit walk (kmsel::lane_hits), the sizes, their exclusive scan, and every word of the gather
 // (kmsel::gather_word).  Every array has exactly the size of its device buffer, reads and writes go through at(), and
@@ -102,11 +102,8 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> all_hits;
     std::string out_all;
     for (uint64_t pos = 0; pos < text_len;) {
-      uint64_t take = text_len - pos;
-      if (take > stage) {
-        take = kmcut::cut(all.data() + pos, stage);
-        if (take == 0) die("no record ends within a staging buffer");
-      }
+      const uint64_t take = kmcut::next_piece(all.data(), pos, text_len, stage);
+      if (take == 0) die("no record ends within a staging buffer");
       ++pieces;
       const uint32_t n = (uint32_t)take;
       // ---- the buffers, as the device has them

@@ -570,6 +570,36 @@ int km_counter_set_jf(km_counter_t* c, const char* path, int op, uint64_t* n_rec
  * (km_counter_records, km_counter_write_jf, km_counter_histo, km_counter_dump) works on what was kept. */
 int km_counter_finish_range(km_counter_t* c, uint32_t lower_count, uint32_t upper_count, kmjf_t** out);
 
+/* ---- counting only a given set of k-mers -----------------------------------------------------------
+ * What `jellyfish count --if FILE` is for ("Filtered counting"): a counter may be given a FILTER once,
+ * before it has been fed anything.  The filter is a set of k-mers in the counter's key encoding; for a canonical
+ * counter a key is replaced by min(key, reverse complement) on the device, so the caller need not canonicalise.  Keys
+ * may repeat; an empty set is a valid filter and counts nothing.  From then on km_counter_add_bases / _add_text /
+ * _add_fastq (with its quality masking as before) add 1 to a window's key ONLY IF THAT KEY IS IN THE FILTER.  Every
+ * key of the filter is in the table from the start with count 0, so km_counter_finish with lower_count 0 lists the
+ * keys that never occurred with count 0 (T^32 of a non-canonical k = 32 counter too, when the filter holds it), and the
+ * kmjf_t finished that way answers 0 for them, as for an absent key.  km_counter_stats_t keeps its meaning: bases and
+ * kmers are all bases and all valid windows seen, distinct is the number of distinct filter keys, slots is fixed by
+ * this call at the smallest power of two >= max(64, 2 * distinct), and n_grow stays 0: the table never grows.
+ * km_counter_finish / _finish_range, _records, _write_jf, _dump and _histo work as on any counter.
+ * State (each refusal before any device work, the counter left as it was and still usable): a counter that has been
+ * fed refuses a filter, a second filter is refused, and a counter with a filter refuses km_counter_add_records,
+ * _add_jf, _set_records and _set_jf (all KM_E_STATE).  KM_E_ARG for NULL arguments and for a key >= 4^k.
+ * The counting pass runs in one of two tiers over the same table: while slots <= 8192 (at most 4096 distinct keys) a
+ * block keeps the table's keys in LDS and touches HBM for a hit alone; a larger set is looked up in HBM.  Either tier
+ * leaves the same table.  KM_COUNT_FILTER_LDS=0 in the environment of this call forces the HBM tier and
+ * KM_COUNT_FILTER_BLOCKS=n caps the grid; neither changes a result.
+ * These semantics are THIS PROJECT'S READING of `--if`, not checked against a run of Jellyfish. */
+int km_counter_set_filter(km_counter_t* c, const uint64_t* keys, uint64_t n);
+/* Waits for everything added so far.  *n_keys: the distinct keys of the filter (0 without one); *kmers_hit: the
+ * windows counted, i.e. the sum of all counts; *tier: 0 no filter, 1 LDS, 2 HBM; *lds_keys: the most distinct keys the
+ * LDS tier takes (a constant of the library, answered with or without a filter); *kernel_ms: with
+ * KM_COUNT_TIME_FILTER=1 in the environment of km_counter_create, the time of the counting kernels (filtered, or the
+ * plain insert kernel of a counter without a filter) by HIP events on the counter's stream, 0 otherwise.  Any output
+ * may be NULL. */
+int km_counter_filter_stats(km_counter_t* c, uint64_t* n_keys, uint64_t* kmers_hit, int* tier /* 0 none, 1 LDS, 2 HBM */,
+                            uint64_t* lds_keys /* most distinct keys the LDS tier takes */, float* kernel_ms);
+
 /* ---- histogram of counts and table statistics -----------------------------------------------------
  * What `jellyfish histo` and `jellyfish stats` print, from counts that are already in HBM or from a file streamed
  * through it ("Histogram and statistics").  Both definitions are THIS PROJECT'S READING of the two

@@ -337,16 +337,27 @@ def main_count(args, err=None):
     is sorted by key, which real Jellyfish could not query (km_amd.count.write_records); with --jellyfish-order
     it is sorted on the device into Jellyfish's own record order and written from there (Counter.write_jf).
     -Q CHAR (Jellyfish's --min-qual-char, as in example/run_leucegene.sh:22): FASTQ files are parsed on the GPU and
-    a base whose quality character is below CHAR is read as N (Counter.add_fastq)."""
+    a base whose quality character is below CHAR is read as N (Counter.add_fastq).
+    --if FILE (Jellyfish's "count only k-mers in this file", may repeat): only the k-mers of the FILEs are counted
+    (FASTA records, or the keys of a .jf of the same -m and -C; Counter.set_filter), each of them is a record and -L 0
+    writes the whole set with its zeros; -s is ignored.  This project's reading of --if, not checked against a run of
+    Jellyfish."""
     err = sys.stderr if err is None else err
     from . import count as kc
+    only = None
+    if args.only:
+        try:                                            # (before the GPU is touched and before the output exists)
+            only = kc.filter_keys(args.only, args.mer_len, args.canonical)
+        except (OSError, ValueError) as e:
+            sys.exit("ERROR: count: %s" % e)
     db, stats, counter = kc.count_files(args.reads, k=args.mer_len, canonical=args.canonical,
                                         lower_count=args.lower_count, device=default_device(),
                                         expected_distinct=args.size, keep_counter=True,
-                                        min_qual_char=args.min_qual_char)
+                                        min_qual_char=args.min_qual_char, only=only)
     cmdline = ["km_amd", "count", "-m", str(args.mer_len)] + (["-C"] if args.canonical else []) + [
         "-L", str(args.lower_count), "-s", str(args.size)] + (
         ["-Q", args.min_qual_char] if args.min_qual_char is not None else []) + (
+        [a for f in args.only or () for a in ("--if", f)]) + (
         ["--jellyfish-order"] if args.jellyfish_order else []) + ["-o", args.output] + list(args.reads)
     try:
         if args.jellyfish_order:
@@ -362,6 +373,9 @@ def main_count(args, err=None):
         err.write("#%s:%d\n" % (key, stats[key]))
     if args.min_qual_char is not None:
         err.write("#min_qual_char:%s\n" % args.min_qual_char)
+    if only is not None:
+        err.write("#filter_kmers:%d\n#kmers_hit:%d\n#filter_tier:%s\n" % (
+            stats["filter_kmers"], stats["kmers_hit"], stats["filter_tier"]))
     if not args.jellyfish_order:
         kc.write_records(args.output, keys, counts, args.mer_len, args.canonical, cmdline=cmdline)
     if args.dump:                                       # of the file just written: its records in its order
@@ -568,13 +582,17 @@ def build_parser():
     ct.add_argument("-m", "--mer-len", type=int, default=31, help="length of mer (default: -m 31)")
     ct.add_argument("-C", "--canonical", action="store_true", help="count both strands, canonical representation")
     ct.add_argument("-L", "--lower-count", type=int, default=1, help="don't output k-mers with count < lower-count")
-    ct.add_argument("-s", "--size", type=int, default=0, help="expected number of distinct k-mers (0: grow as needed)")
+    ct.add_argument("-s", "--size", type=int, default=0,
+                    help="expected number of distinct k-mers (0: grow as needed); ignored with --if, whose set sizes the table")
     ct.add_argument("-o", "--output", default="mer_counts.jf", help="output file (default: mer_counts.jf)")
     ct.add_argument("--jellyfish-order", action="store_true",
                     help="write the records in Jellyfish's own order (matrix position, then key), sorted on the GPU")
     ct.add_argument("-Q", "--min-qual-char", type=_one_char, default=None, metavar="CHAR",
                     help="a base of a FASTQ read whose quality character is below CHAR is read as N (FASTQ is then "
                          "parsed on the GPU; no effect on FASTA)")
+    ct.add_argument("--if", dest="only", action="append", default=None, metavar="FILE",
+                    help="count only the k-mers of FILE (FASTA, or a .jf of the same -m / -C); may be repeated; every "
+                         "k-mer of the set is a record, so -L 0 writes those that never occurred with count 0")
     ct.add_argument("--histo", metavar="FILE", default=None,
                     help="also write the histogram of the counts written (after -L), as `histo OUT` prints it")
     ct.add_argument("--dump", metavar="FILE", default=None,

@@ -56,20 +56,71 @@ def feed_file(counter, path, block=BLOCK, min_qual_char=None):
         blocks.close()
 
 
+def filter_keys(only, k, canonical):
+    """The key array of count_files' `only`, on the host and without a GPU: a uint64 array goes through as it is; a
+    path, or a list of paths, gives the keys of its files in the order given.  A file whose first non-blank byte is
+    '>' (plain or gzip) is FASTA and gives the k-mers of each of its records (query_keys); any other file must be a
+    `binary/sorted` file and gives the keys of its records (one with count 0 is absent, as for every reader here), and
+    its k and canonical setting must equal (k, canonical).  OSError for a missing file, ValueError for a foreign one or
+    one of another k / canonical."""
+    if isinstance(only, np.ndarray):
+        return np.ascontiguousarray(only, np.uint64).reshape(-1)
+    if isinstance(only, (str, bytes, os.PathLike)):
+        only = [only]
+    only = list(only)
+    if only and all(isinstance(v, (int, np.integer)) for v in only):
+        return np.array(only, np.uint64)
+    parts = []
+    for path in only:
+        fh, close = _open(path)
+        try:
+            head = fh.read(1 << 12).lstrip(b"\r\n \t")
+        finally:
+            if close:
+                fh.close()
+        if head[:1] == b">":
+            parts.append(query_keys(k, canonical, seq_files=[path]))
+            continue
+        try:
+            info = _lib.jf_file_info(path)
+        except _lib.KmError as e:
+            raise ValueError("%s is neither FASTA nor a binary/sorted file (%s)" % (path, e.detail)) from e
+        if (info["k"], info["canonical"]) != (int(k), bool(canonical)):
+            raise ValueError("%s holds k=%d canonical=%s, but the k-mers are counted with k=%d canonical=%s" % (
+                path, info["k"], info["canonical"], k, bool(canonical)))
+        db = _lib.Database.open(path)
+        try:
+            parts.append(np.array(db.records()[0], np.uint64))
+        finally:
+            db.close()
+    return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, np.uint64), np.uint64)
+
+
 def count_files(paths, k=31, canonical=True, lower_count=1, device=0, expected_distinct=0, keep_counter=False,
-                min_qual_char=None):
+                min_qual_char=None, only=None):
     """Count the k-mers of every read of `paths` (FASTA or 4-line FASTQ, gzip recognised by its magic, '-' =
     stdin) -> (Database, stats).  stats is the dict of Counter.stats() before the cut at lower_count.
     keep_counter=True returns (Database, stats, Counter) so that the caller can fetch the records.
     min_qual_char (an int or one character; Jellyfish's -Q): FASTQ files are parsed on the GPU (Counter.add_fastq)
-    and a base whose quality byte is below it is read as N; None: the host stripper, qualities never looked at."""
+    and a base whose quality byte is below it is read as N; None: the host stripper, qualities never looked at.
+    only (Jellyfish's --if; a uint64 array of keys, or paths as filter_keys reads them): count only these k-mers
+    (Counter.set_filter).  Each of them is a record, with count 0 if it never occurred, so lower_count=0 lists the whole
+    set; expected_distinct is ignored, the table is sized by the set.  stats gains filter_kmers, kmers_hit and
+    filter_tier.  Everything about `only` that can fail fails before a counter exists."""
     if isinstance(paths, (str, bytes)):
         paths = [paths]
-    counter = _lib.Counter(k=k, canonical=canonical, device=device, expected_distinct=expected_distinct)
+    keys = None if only is None else filter_keys(only, k, canonical)
+    counter = _lib.Counter(k=k, canonical=canonical, device=device,
+                           expected_distinct=expected_distinct if keys is None else 1)
     try:
+        if keys is not None:
+            counter.set_filter(keys)
         for p in paths:
             feed_file(counter, p, min_qual_char=min_qual_char)
         stats = counter.stats()
+        if keys is not None:
+            fs = counter.filter_stats()
+            stats.update(filter_kmers=fs["n_keys"], kmers_hit=fs["kmers_hit"], filter_tier=fs["tier"])
         db = counter.finish(lower_count)
     except BaseException:
         counter.close()

@@ -59,6 +59,9 @@ struct km_counter {
   int feed = FEED_NONE;                   // what the counter has taken: the two kinds do not mix (setops_host.h)
   int set_op = 0;                         // FEED_SET: KM_SET_INTERSECT / KM_SET_SUBTRACT
   uint32_t set_inputs = 0;                // FEED_SET: inputs so far, the empty ones too
+  int filter_tier = 0;                    // filter_host.h: 0 no filter, 1 the LDS tier, 2 the HBM tier
+  uint32_t filter_blocks = 0;             // ... the most blocks of a filtered launch
+  KernelSpans insert_spans;               // KM_COUNT_TIME_FILTER: around every insert launch, filtered or not
   DevBuf<uint64_t> out_keys;
   DevBuf<uint32_t> out_counts;
   uint64_t n_out = 0;
@@ -87,6 +90,14 @@ static int counter_takes_plain(const km_counter* c) {
   if (c->feed == FEED_SET)
     return fail(KM_E_STATE, "counter holds the inputs of a set operation (%s): it takes no text, FASTQ or sum / max records",
                 c->set_op == KM_SET_INTERSECT ? "intersect" : "subtract");
+  return KM_OK;
+}
+
+// ... and every call that feeds records, of either kind: a filter restricts what is counted from reads, and a
+// record brings a count of its own (filter_host.h)
+static int counter_takes_records(const km_counter* c) {
+  if (c->filter_tier)
+    return fail(KM_E_STATE, "counter has a filter: it counts reads (add_bases, add_text, add_fastq) and takes no records");
   return KM_OK;
 }
 
@@ -141,13 +152,20 @@ static int counter_reserve(km_counter* c, uint64_t windows) {
   return KM_OK;
 }
 
+static void launch_filtered(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from);   // filter_host.h
+
 // text[0 .. n) on the device into the table; the windows that start before own_from belong to the piece before.
+// A counter with a filter only looks its keys up (filter_kernel.h).
 static int launch_insert(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from) {
   const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
-  hipLaunchKernelGGL(k_count_insert, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, c->st, text, n, own_from,
-                     c->k, c->canonical, c->table.p, c->slots - 1, c->meta.p);
+  KMCHK(c->insert_spans.open(c->st));
+  if (c->filter_tier)
+    launch_filtered(c, text, n, own_from);
+  else
+    hipLaunchKernelGGL(k_count_insert, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, c->st, text, n, own_from,
+                       c->k, c->canonical, c->table.p, c->slots - 1, c->meta.p);
   HIPCHK(hipGetLastError());
-  return KM_OK;
+  return c->insert_spans.close(c->st);
 }
 
 // Enqueue the piece of add_bases / add_text (copy + insert) and turn to the other buffer, which starts with the
@@ -156,7 +174,7 @@ static int counter_flush(km_counter* c) {
   if (c->fill <= c->own_from) return KM_OK;
   const uint64_t n = c->fill;
   const unsigned char* sent = c->stg.mine;            // (a buffer whose copy is in flight may still be read)
-  KMCHK(counter_reserve(c, n >= (uint64_t)c->k ? n - c->k + 1 : 0));
+  if (!c->filter_tier) KMCHK(counter_reserve(c, n >= (uint64_t)c->k ? n - c->k + 1 : 0));   // (a filter's table never grows)
   KMCHK(c->stg.ship(c->d_text, n, c->st));
   KMCHK(launch_insert(c, c->d_text, n, c->own_from));
   KMCHK(c->stg.claim());
@@ -204,6 +222,7 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
   c->k = k;
   c->canonical = canonical ? 1 : 0;
   if (const char* e = getenv("KM_COUNT_TIME_MERGE")) c->merge_spans.timed = atoi(e) != 0;
+  if (const char* e = getenv("KM_COUNT_TIME_FILTER")) c->insert_spans.timed = atoi(e) != 0;
   c->slots = COUNT_DEFAULT_SLOTS;
   if (expected_distinct) {
     c->slots = 64;
@@ -328,7 +347,7 @@ static int fastq_enqueue(km_counter* c, const char* text, uint64_t n, uint64_t b
   FastqDev& f = *c->fq;
   KMCHK(c->stg.claim());
   memcpy(c->stg.mine, text, n);
-  KMCHK(counter_reserve(c, n));                         // every byte taken as a window: a bound, and a loose one
+  if (!c->filter_tier) KMCHK(counter_reserve(c, n));    // every byte taken as a window: a bound, and a loose one
   KMCHK(c->stg.ship(c->d_text, n, c->st));
   KMCHK(c->fq_spans.open(c->st));
   KMCHK(fastq_front(f, c->d_text.p, n, base, min_qual, c->meta.p + CM_FORMAT, c->st, nullptr));
@@ -430,8 +449,9 @@ static int counter_finish_cut(km_counter* c, uint32_t lower_count, uint32_t uppe
   KMCHK(counter_read_meta(c, m));
   uint64_t n = m[CM_OUT];
   if (n > m[CM_DISTINCT]) return fail(KM_E_HIP, "compaction wrote %llu records for %llu keys", m[CM_OUT], m[CM_DISTINCT]);
-  // T^32 of a non-canonical k = 32 table (count_kernel.h; under a set operation its cells are those of setops_kernel.h)
-  const bool have = intersect ? m[CM_ALLT_HAVE] != 0 : m[CM_ALLT] != 0;
+  // T^32 of a non-canonical k = 32 table (count_kernel.h; under a set operation its cells are those of setops_kernel.h,
+  // and a filter that holds it lists it with whatever count it has, 0 too)
+  const bool have = intersect || c->filter_tier ? m[CM_ALLT_HAVE] != 0 : m[CM_ALLT] != 0;
   const uint32_t allt = intersect ? ~(uint32_t)m[CM_ALLT] : (uint32_t)std::min<unsigned long long>(m[CM_ALLT], 0xFFFFFFFFull);
   if (have && m[CM_ALLT_MATCH] == want && allt >= lower_count && allt <= upper_count) {
     const uint64_t key = EMPTY;

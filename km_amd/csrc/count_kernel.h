@@ -24,9 +24,11 @@ constexpr uint32_t COUNT_PAD = 128;     // readable bytes behind a staged chunk 
 // cells of the counter's device meta block (u64 each)
 // (CM_FORMAT: fastq_kernel.h's smallest (stream offset << 8 | kind), ~0 while the text is well-formed)
 // (CM_RECORDS: merge_kernel.h's tally of the records taken; CM_BASES / CM_KMERS tally text only)
-// (CM_ALLT_HAVE / CM_ALLT_MATCH: setops_kernel.h's "claimed" and spare word of the key ~0, which has no slot)
+// (CM_ALLT_HAVE / CM_ALLT_MATCH: setops_kernel.h's "claimed" and spare word of the key ~0, which has no slot;
+//  filter_kernel.h: CM_ALLT_HAVE = the key ~0 is in the filter)
+// (CM_HITS: filter_kernel.h's tally of the windows whose key was in the filter)
 enum { CM_DISTINCT = 0, CM_BASES = 1, CM_KMERS = 2, CM_ALLT = 3, CM_ERROR = 4, CM_OUT = 5, CM_FORMAT = 6, CM_RECORDS = 7,
-       CM_ALLT_HAVE = 8, CM_ALLT_MATCH = 9, CM_WORDS = 10 };
+       CM_ALLT_HAVE = 8, CM_ALLT_MATCH = 9, CM_HITS = 10, CM_WORDS = 11 };
 
 __global__ void k_count_init(CountSlot* slots, uint64_t n_slots) {
   uint4* p = reinterpret_cast<uint4*>(slots);

@@ -27,6 +27,8 @@
 //                  (count_host.h's front half of a FASTQ piece, a Staging in, the kept bytes out through TextDrain)
 //   select_pair_host.h  km_select_pair_*: the same for the two mate streams of a paired-end run, kept or dropped as
 //                  pairs (select_host.h's SelDev per mate, a Staging in and a TextDrain out per mate)
+//   filter_host.h  km_counter_set_filter, km_counter_filter_stats: a counter that counts only a given set of k-mers
+//                  (the seed of its table; launch_filtered, which count_host.h's launch_insert calls)
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
 #include <hip/hip_runtime.h>
@@ -74,6 +76,7 @@
 #include "select_rule.h"
 #include "select_pair_kernel.h"
 #include "select_pair_rule.h"
+#include "filter_kernel.h"      // (last: every kernel before it keeps its place in the code object)
 
 using namespace kmd;
 
@@ -92,3 +95,4 @@ using namespace kmd;
 #include "scan_host.h"
 #include "select_host.h"
 #include "select_pair_host.h"
+#include "filter_host.h"        // (last: k_count_filtered's two instances enter the code object behind all others)

@@ -9,7 +9,8 @@ namespace {
 // What every add_* checks first, in their order.
 int merge_check(const km_counter* c, int mode) {
   if (mode != KM_MERGE_SUM && mode != KM_MERGE_MAX) return fail(KM_E_ARG, "mode %d is neither KM_MERGE_SUM nor KM_MERGE_MAX", mode);
-  return counter_takes_plain(c);
+  KMCHK(counter_takes_plain(c));
+  return counter_takes_records(c);
 }
 
 // n records of kb + cb bytes; fill(dst, piece) writes piece.bytes bytes of them to a pinned buffer.

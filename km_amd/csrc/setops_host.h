@@ -12,6 +12,7 @@ int set_check(const km_counter* c, int op) {
   if (op != KM_SET_INTERSECT && op != KM_SET_SUBTRACT)
     return fail(KM_E_ARG, "op %d is neither KM_SET_INTERSECT nor KM_SET_SUBTRACT", op);
   KMCHK(counter_usable(c));
+  KMCHK(counter_takes_records(c));
   if (c->feed == FEED_PLAIN)
     return fail(KM_E_STATE, "counter has taken text, FASTQ or sum / max records: a set operation (%s) needs a counter of its own",
                 set_name(op));

@@ -45,6 +45,7 @@ SYMBOLS = [
     "km_counter_write_jf",
     "km_jf_file_info", "km_counter_add_records", "km_counter_add_jf", "km_counter_merge_stats",
     "km_counter_set_records", "km_counter_set_jf", "km_counter_finish_range",
+    "km_counter_set_filter", "km_counter_filter_stats",
     "km_histo_layout", "km_counter_histo", "km_jf_histo", "km_histo_kernel_ms", "km_histo_text", "km_histo_stats_text",
     "km_dump_text", "km_jf_dump", "km_counter_dump", "kmjf_query_text", "km_dump_kernel_ms",
     "kmjf_cov_seqs", "kmjf_scan_text", "km_scan_kernel_ms",
@@ -318,6 +319,9 @@ def load():
         "km_counter_set_records": [vp, vp, vp, u64, i32],
         "km_counter_set_jf": [vp, cp, i32, C.POINTER(u64)],
         "km_counter_finish_range": [vp, u32, u32, C.POINTER(vp)],
+        "km_counter_set_filter": [vp, vp, u64],
+        "km_counter_filter_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64),
+                                    C.POINTER(C.c_float)],
         "km_histo_layout": [u64, u64, u64, C.POINTER(u64), C.POINTER(u64)],
         "km_counter_histo": [vp, u64, u64, u64, u32, u32, vp, u64, C.POINTER(HistoStats)],
         "km_jf_histo": [i32, cp, u64, u64, u64, u32, u32, vp, u64, C.POINTER(HistoStats), C.POINTER(C.c_int32),
@@ -698,6 +702,24 @@ class Counter(_Handle):
         check(self._lib.km_counter_set_jf(self._c, os.fsencode(path), _set_op(op), C.byref(n)))
         return int(n.value)
 
+    def set_filter(self, keys):
+        """km_counter_set_filter: from now on only the k-mers of `keys` (uint64, the counter's key encoding; a
+        canonical counter canonicalises them on the device; repeats allowed, empty allowed) are counted, and each of
+        them is in the table from the start with count 0.  Once, and before anything has been fed.  This project's
+        reading of `jellyfish count --if`."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        check(self._lib.km_counter_set_filter(self._c, ptr(keys) if keys.size else None, keys.size))
+
+    def filter_stats(self):
+        """km_counter_filter_stats (waits for everything added so far): dict(n_keys = distinct filter keys, kmers_hit
+        = windows counted, tier = "none" / "lds" / "hbm", lds_keys = the most distinct keys the LDS tier takes,
+        kernel_ms = the time of the counting kernels, needs KM_COUNT_TIME_FILTER=1 when the counter is made)."""
+        n, hit, tier, cap, ms = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_uint64(), C.c_float()
+        check(self._lib.km_counter_filter_stats(self._c, C.byref(n), C.byref(hit), C.byref(tier), C.byref(cap),
+                                                C.byref(ms)))
+        return {"n_keys": int(n.value), "kmers_hit": int(hit.value), "tier": FILTER_TIERS[tier.value],
+                "lds_keys": int(cap.value), "kernel_ms": float(ms.value)}
+
     def merge_stats(self):
         """km_counter_merge_stats (waits for everything added so far): dict(records_in = records with count > 0
         taken by add_records / add_jf / set_records / set_jf, kernel_ms = the time of their kernels, needs
@@ -979,6 +1001,7 @@ def _merge_mode(mode):
 
 
 SET_OPS = {"intersect": 0, "subtract": 1}   # KM_SET_INTERSECT, KM_SET_SUBTRACT
+FILTER_TIERS = ("none", "lds", "hbm")       # km_counter_filter_stats' tier
 
 
 def _set_op(op):

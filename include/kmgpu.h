@@ -600,6 +600,50 @@ int km_counter_set_filter(km_counter_t* c, const uint64_t* keys, uint64_t n);
 int km_counter_filter_stats(km_counter_t* c, uint64_t* n_keys, uint64_t* kmers_hit, int* tier /* 0 none, 1 LDS, 2 HBM */,
                             uint64_t* lds_keys /* most distinct keys the LDS tier takes */, float* kernel_ms);
 
+/* ---- solid k-mers: keeping the k-mers seen once out of the table, in two passes ------------------
+ * What `jellyfish bc` + `jellyfish count --bc` are for ("Solid k-mers, two passes"): in real reads most
+ * distinct k-mers are sequencing errors that occur once, and every user of a table cuts them away.  A counter may be
+ * given a SKETCH once, before it has been fed anything and instead of a filter.  It is then fed TWICE: everything fed
+ * until km_counter_sketch_done (pass 1) is only noted in the sketch, everything fed after it (pass 2) is counted, but
+ * a window adds 1 to its key ONLY IF THE SKETCH ADMITS THE KEY.  The sketch admits every key that pass 1 saw at least
+ * twice (no false negatives) and a few that it saw once or never (false positives, counted exactly like any key).
+ * So when pass 2 is fed what pass 1 was fed, the records of km_counter_finish with lower_count >= 2 are exactly those
+ * of a plain counter, while the table holds, and grows for, the admitted keys alone.  With lower_count < 2 the records
+ * are a subset: the caller of this interface wants lower_count >= 2.  If pass 2 is fed OTHER text than pass 1, the
+ * result is "the counts, in the second text, of the k-mers the first text admitted"; that is no error.
+ * The rule (km_amd/csrc/sketch_rule.h; km_sketch_slot and km_sketch_words state it on the host):
+ *   the sketch is `words` 64-bit words, a power of two, 64 <= words <= 2^40; the low 32 bits of a word are plane 1
+ *   ("seen"), the high 32 bits plane 2 ("seen again");
+ *   a key's slot: h = mix64(key ^ 0x9E3779B97F4A7C15) (the MurmurHash3 finalizer), word = h >> (64 - log2 words),
+ *   mask = 1 << (h & 31) | 1 << (h >> 5 & 31) | 1 << (h >> 10 & 31), one to three bits;
+ *   noting a key: if plane 2 of its word holds the mask already, nothing; otherwise the mask is OR-ed into plane 1
+ *   atomically, and if plane 1 held it before, into plane 2 as well;
+ *   the sketch admits a key iff plane 2 of its word holds its mask;
+ *   km_sketch_words(n) = the smallest power of two >= max(64, ceil(n / 2)): two expected distinct k-mers per word.
+ * T^32 of a non-canonical k = 32 counter (the key ~0) has no sketch entry: pass 2 always counts it, in its own cell.
+ * Pass 1: km_counter_add_bases / _add_text / _add_fastq (with its quality masking) work as on any counter, and a
+ * malformed FASTQ record is reported by this pass (km_counter_sketch_done at the latest).  bases and kmers of
+ * km_counter_stats_t are tallied by pass 2 alone; distinct, slots and n_grow speak of the admitted keys.
+ * State (each refusal before any device work, the counter left as it was and still usable; all KM_E_STATE):
+ * km_counter_set_sketch on a counter that has been fed, has a sketch or has a filter; km_counter_set_filter,
+ * _add_records, _add_jf, _set_records, _set_jf on a counter with a sketch; km_counter_finish / _finish_range, _records,
+ * _histo, _dump, _write_jf before km_counter_sketch_done; km_counter_sketch_done twice or without a sketch.  KM_E_ARG
+ * for a `words` that is no power of two or out of range.  KM_COUNT_FILTER_BLOCKS=n caps the grid of pass 1 too.
+ * The flag and these semantics are THIS PROJECT'S OWN, not checked against a run of Jellyfish. */
+int km_sketch_words(uint64_t expected_distinct, uint64_t* words);
+int km_sketch_slot(uint64_t key, uint64_t words, uint64_t* word, uint32_t* mask);
+int km_counter_set_sketch(km_counter_t* c, uint64_t words);
+/* Ends pass 1: everything fed is enqueued and waited for, and the next add_* call starts a fresh stream (no k-mer
+ * spans the two passes, a FASTQ stream's offsets start at 0 again). */
+int km_counter_sketch_done(km_counter_t* c);
+/* Waits for everything added so far.  *words: the sketch's size (0 without one); *bits_1 / *bits_2: the set bits of
+ * plane 1 / plane 2 (final once pass 1 has ended); *kmers_noted: the windows pass 1 noted (all valid windows but those
+ * of the key ~0); *kmers_admitted: the windows pass 2 counted in the table; kernel_ms[0], kernel_ms[1]: with
+ * KM_COUNT_TIME_FILTER=1 in the environment of km_counter_create, the time of the kernels of pass 1 and of pass 2 by
+ * HIP events on the counter's stream, 0 otherwise.  Any output may be NULL. */
+int km_counter_sketch_stats(km_counter_t* c, uint64_t* words, uint64_t* bits_1, uint64_t* bits_2, uint64_t* kmers_noted,
+                            uint64_t* kmers_admitted, float* kernel_ms /* [2] */);
+
 /* ---- histogram of counts and table statistics -----------------------------------------------------
  * What `jellyfish histo` and `jellyfish stats` print, from counts that are already in HBM or from a file streamed
  * through it ("Histogram and statistics").  Both definitions are THIS PROJECT'S READING of the two

@@ -341,7 +341,11 @@ def main_count(args, err=None):
     --if FILE (Jellyfish's "count only k-mers in this file", may repeat): only the k-mers of the FILEs are counted
     (FASTA records, or the keys of a .jf of the same -m and -C; Counter.set_filter), each of them is a record and -L 0
     writes the whole set with its zeros; -s is ignored.  This project's reading of --if, not checked against a run of
-    Jellyfish."""
+    Jellyfish.
+    --solid N (this project's own flag; the job of `jellyfish bc` + `count --bc`): the reads are read twice, a first
+    pass notes their k-mers in a Bloom sketch sized for N distinct k-mers, the second counts only those seen again
+    (Counter.set_sketch).  The records are those of the same command without --solid at -L max(2, -L), which is the
+    -L that is applied and written into the header; the table never holds the k-mers seen once."""
     err = sys.stderr if err is None else err
     from . import count as kc
     only = None
@@ -350,14 +354,22 @@ def main_count(args, err=None):
             only = kc.filter_keys(args.only, args.mer_len, args.canonical)
         except (OSError, ValueError) as e:
             sys.exit("ERROR: count: %s" % e)
-    db, stats, counter = kc.count_files(args.reads, k=args.mer_len, canonical=args.canonical,
-                                        lower_count=args.lower_count, device=default_device(),
-                                        expected_distinct=args.size, keep_counter=True,
-                                        min_qual_char=args.min_qual_char, only=only)
+    solid = args.solid
+    lower_count = args.lower_count if solid is None else max(2, args.lower_count)
+    try:
+        db, stats, counter = kc.count_files(args.reads, k=args.mer_len, canonical=args.canonical,
+                                            lower_count=lower_count, device=default_device(),
+                                            expected_distinct=args.size, keep_counter=True,
+                                            min_qual_char=args.min_qual_char, only=only, solid=solid)
+    except ValueError as e:
+        if solid is None:
+            raise
+        sys.exit("ERROR: count: %s" % e)
     cmdline = ["km_amd", "count", "-m", str(args.mer_len)] + (["-C"] if args.canonical else []) + [
-        "-L", str(args.lower_count), "-s", str(args.size)] + (
+        "-L", str(lower_count), "-s", str(args.size)] + (
         ["-Q", args.min_qual_char] if args.min_qual_char is not None else []) + (
         [a for f in args.only or () for a in ("--if", f)]) + (
+        ["--solid", str(solid)] if solid is not None else []) + (
         ["--jellyfish-order"] if args.jellyfish_order else []) + ["-o", args.output] + list(args.reads)
     try:
         if args.jellyfish_order:
@@ -376,6 +388,9 @@ def main_count(args, err=None):
     if only is not None:
         err.write("#filter_kmers:%d\n#kmers_hit:%d\n#filter_tier:%s\n" % (
             stats["filter_kmers"], stats["kmers_hit"], stats["filter_tier"]))
+    if solid is not None:
+        for key in ("lower_count", "sketch_words", "sketch_bits_1", "sketch_bits_2", "kmers_admitted"):
+            err.write("#%s:%d\n" % (key, stats[key]))
     if not args.jellyfish_order:
         kc.write_records(args.output, keys, counts, args.mer_len, args.canonical, cmdline=cmdline)
     if args.dump:                                       # of the file just written: its records in its order
@@ -593,6 +608,10 @@ def build_parser():
     ct.add_argument("--if", dest="only", action="append", default=None, metavar="FILE",
                     help="count only the k-mers of FILE (FASTA, or a .jf of the same -m / -C); may be repeated; every "
                          "k-mer of the set is a record, so -L 0 writes those that never occurred with count 0")
+    ct.add_argument("--solid", type=_count_value, default=None, metavar="N",
+                    help="keep the k-mers seen once out of the table: read the reads twice, note their k-mers in a Bloom "
+                         "sketch sized for N expected distinct k-mers, count those seen again; -L is at least 2 then, and "
+                         "-s speaks of the k-mers seen twice; not with --if or standard input")
     ct.add_argument("--histo", metavar="FILE", default=None,
                     help="also write the histogram of the counts written (after -L), as `histo OUT` prints it")
     ct.add_argument("--dump", metavar="FILE", default=None,
@@ -690,7 +709,7 @@ def _looks_like_target(path):
 
 def parse_args(argv=None, parser=None):
     """build_parser().parse_args plus what argparse cannot say on its own, refused the same way (exit status 2):
-    `dump -t` without `-c`, `query` with neither -s nor a MER, `merge` with more than one of --max / --min /
+    `dump -t` without `-c`, `query` with neither -s nor a MER, `count` with --solid beside --if, `merge` with more than one of --max / --min /
     --subtract, `bait` without exactly one of -t / -d or with -m beside -d, without reads, with unequal numbers of -1 and
     -2, with plain reads beside them, with -1/-2 but not both of -o and -O or with one path for both, and with -O,
     --pair-rule or --no-name-check but no -1/-2."""
@@ -698,6 +717,8 @@ def parse_args(argv=None, parser=None):
     args = parser.parse_args(argv)
     if args._cmd == "dump" and args.tab and not args.column:
         parser.error("dump: -t needs -c")
+    if args._cmd == "count" and args.solid is not None and args.only:
+        parser.error("count: --solid and --if exclude each other")
     if args._cmd == "merge" and args.max + args.min + args.subtract > 1:
         parser.error("merge: --max, --min and --subtract exclude each other")
     if args._cmd == "query" and not args.sequence and not args.mers:

@@ -97,7 +97,7 @@ def filter_keys(only, k, canonical):
 
 
 def count_files(paths, k=31, canonical=True, lower_count=1, device=0, expected_distinct=0, keep_counter=False,
-                min_qual_char=None, only=None):
+                min_qual_char=None, only=None, solid=None):
     """Count the k-mers of every read of `paths` (FASTA or 4-line FASTQ, gzip recognised by its magic, '-' =
     stdin) -> (Database, stats).  stats is the dict of Counter.stats() before the cut at lower_count.
     keep_counter=True returns (Database, stats, Counter) so that the caller can fetch the records.
@@ -106,21 +106,47 @@ def count_files(paths, k=31, canonical=True, lower_count=1, device=0, expected_d
     only (Jellyfish's --if; a uint64 array of keys, or paths as filter_keys reads them): count only these k-mers
     (Counter.set_filter).  Each of them is a record, with count 0 if it never occurred, so lower_count=0 lists the whole
     set; expected_distinct is ignored, the table is sized by the set.  stats gains filter_kmers, kmers_hit and
-    filter_tier.  Everything about `only` that can fail fails before a counter exists."""
+    filter_tier.  Everything about `only` that can fail fails before a counter exists.
+    solid (an int N, the expected number of distinct k-mers in the reads; this project's own): the k-mers seen once stay
+    out of the table.  Every path is fed twice: a first pass notes the k-mers in a sketch of lib.sketch_words(N) words
+    (Counter.set_sketch), the second counts those the sketch saw again.  The records are exactly those of a plain count
+    cut at max(2, lower_count), which is the cut that is applied; expected_distinct then speaks of the k-mers seen at
+    least twice.  stats gains sketch_words, sketch_bits_1, sketch_bits_2, kmers_admitted and lower_count (the
+    effective one).  A path '-' (stdin cannot be read twice) and `solid` beside `only` raise ValueError before a counter
+    exists."""
     if isinstance(paths, (str, bytes)):
         paths = [paths]
+    if solid is not None:
+        paths = list(paths)
+        if only is not None:
+            raise ValueError("solid and only exclude each other: a counter takes a sketch or a filter, not both")
+        if "-" in paths:
+            raise ValueError("solid reads every input twice: '-' (standard input) can be read once")
+        if not 0 <= int(solid) <= 1 << 41:
+            raise ValueError("solid=%d: the expected number of distinct k-mers is 0 .. 2^41" % solid)
+        words = _lib.sketch_words(solid)
+        lower_count = max(2, int(lower_count))
     keys = None if only is None else filter_keys(only, k, canonical)
     counter = _lib.Counter(k=k, canonical=canonical, device=device,
                            expected_distinct=expected_distinct if keys is None else 1)
     try:
         if keys is not None:
             counter.set_filter(keys)
+        if solid is not None:
+            counter.set_sketch(words)
+            for p in paths:
+                feed_file(counter, p, min_qual_char=min_qual_char)
+            counter.sketch_done()
         for p in paths:
             feed_file(counter, p, min_qual_char=min_qual_char)
         stats = counter.stats()
         if keys is not None:
             fs = counter.filter_stats()
             stats.update(filter_kmers=fs["n_keys"], kmers_hit=fs["kmers_hit"], filter_tier=fs["tier"])
+        if solid is not None:
+            ss = counter.sketch_stats()
+            stats.update(sketch_words=ss["words"], sketch_bits_1=ss["bits_1"], sketch_bits_2=ss["bits_2"],
+                         kmers_admitted=ss["kmers_admitted"], lower_count=lower_count)
         db = counter.finish(lower_count)
     except BaseException:
         counter.close()

@@ -62,6 +62,11 @@ struct km_counter {
   int filter_tier = 0;                    // filter_host.h: 0 no filter, 1 the LDS tier, 2 the HBM tier
   uint32_t filter_blocks = 0;             // ... the most blocks of a filtered launch
   KernelSpans insert_spans;               // KM_COUNT_TIME_FILTER: around every insert launch, filtered or not
+  int sketch_pass = 0;                    // sketch_host.h: 0 no sketch, 1 the noting pass, 2 the counting pass
+  DevBuf<uint64_t> sketch;                // ... its words (sketch_rule.h)
+  uint64_t sketch_words = 0;
+  uint32_t sketch_blocks = 0;             // ... the most blocks of a noting launch
+  float sketch_note_ms = 0.f;             // ... what insert_spans held when the noting pass ended
   DevBuf<uint64_t> out_keys;
   DevBuf<uint32_t> out_counts;
   uint64_t n_out = 0;
@@ -98,8 +103,20 @@ static int counter_takes_plain(const km_counter* c) {
 static int counter_takes_records(const km_counter* c) {
   if (c->filter_tier)
     return fail(KM_E_STATE, "counter has a filter: it counts reads (add_bases, add_text, add_fastq) and takes no records");
+  if (c->sketch_pass)
+    return fail(KM_E_STATE, "counter has a sketch: it counts reads (add_bases, add_text, add_fastq) and takes no records");
   return KM_OK;
 }
+
+// ... and every call that reads the table or ends the counter: while a sketch is in its noting pass there is no table
+// to speak of (sketch_host.h)
+static int counter_sketch_settled(const km_counter* c) {
+  if (c->sketch_pass == 1) return fail(KM_E_STATE, "the counter's sketch is in its first pass: km_counter_sketch_done comes first");
+  return KM_OK;
+}
+
+// nothing claims a slot: a filter's table never grows, and the noting pass of a sketch does not touch the table
+static bool counter_table_fixed(const km_counter* c) { return c->filter_tier || c->sketch_pass == 1; }
 
 // waits for everything enqueued
 static int counter_read_meta(km_counter* c, unsigned long long* m) {
@@ -153,14 +170,18 @@ static int counter_reserve(km_counter* c, uint64_t windows) {
 }
 
 static void launch_filtered(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from);   // filter_host.h
+static void launch_sketch(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from);     // sketch_host.h
 
 // text[0 .. n) on the device into the table; the windows that start before own_from belong to the piece before.
-// A counter with a filter only looks its keys up (filter_kernel.h).
+// A counter with a filter only looks its keys up (filter_kernel.h); one with a sketch notes the keys in its first pass
+// and counts the admitted ones in its second (sketch_kernel.h).
 static int launch_insert(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from) {
   const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
   KMCHK(c->insert_spans.open(c->st));
   if (c->filter_tier)
     launch_filtered(c, text, n, own_from);
+  else if (c->sketch_pass)
+    launch_sketch(c, text, n, own_from);
   else
     hipLaunchKernelGGL(k_count_insert, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, c->st, text, n, own_from,
                        c->k, c->canonical, c->table.p, c->slots - 1, c->meta.p);
@@ -174,7 +195,7 @@ static int counter_flush(km_counter* c) {
   if (c->fill <= c->own_from) return KM_OK;
   const uint64_t n = c->fill;
   const unsigned char* sent = c->stg.mine;            // (a buffer whose copy is in flight may still be read)
-  if (!c->filter_tier) KMCHK(counter_reserve(c, n >= (uint64_t)c->k ? n - c->k + 1 : 0));   // (a filter's table never grows)
+  if (!counter_table_fixed(c)) KMCHK(counter_reserve(c, n >= (uint64_t)c->k ? n - c->k + 1 : 0));
   KMCHK(c->stg.ship(c->d_text, n, c->st));
   KMCHK(launch_insert(c, c->d_text, n, c->own_from));
   KMCHK(c->stg.claim());
@@ -347,7 +368,7 @@ static int fastq_enqueue(km_counter* c, const char* text, uint64_t n, uint64_t b
   FastqDev& f = *c->fq;
   KMCHK(c->stg.claim());
   memcpy(c->stg.mine, text, n);
-  if (!c->filter_tier) KMCHK(counter_reserve(c, n));    // every byte taken as a window: a bound, and a loose one
+  if (!counter_table_fixed(c)) KMCHK(counter_reserve(c, n));   // every byte taken as a window: a bound, and a loose one
   KMCHK(c->stg.ship(c->d_text, n, c->st));
   KMCHK(c->fq_spans.open(c->st));
   KMCHK(fastq_front(f, c->d_text.p, n, base, min_qual, c->meta.p + CM_FORMAT, c->st, nullptr));
@@ -427,6 +448,7 @@ extern "C" int km_counter_stats(km_counter_t* c, km_counter_stats_t* s) {
 // compaction of setops_kernel.h; without it, the one of count_kernel.h that km_counter_finish has always used.
 static int counter_finish_cut(km_counter* c, uint32_t lower_count, uint32_t upper_count, bool ranged, kmjf_t** out) {
   KMCHK(counter_usable(c));
+  KMCHK(counter_sketch_settled(c));
   HIPCHK(hipSetDevice(c->device));
   int rc = counter_flush(c);
   unsigned long long m[CM_WORDS];
@@ -467,6 +489,7 @@ static int counter_finish_cut(km_counter* c, uint32_t lower_count, uint32_t uppe
   c->n_out = n;
   c->table.release();
   c->d_text.release();
+  c->sketch.release();
   c->fq.reset();
   c->finished = true;
   *out = h;
@@ -480,6 +503,7 @@ extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t**
 
 extern "C" int km_counter_records(km_counter_t* c, uint64_t* keys, uint32_t* counts, uint64_t cap, uint64_t* n) {
   if (!c || !n) return fail(KM_E_ARG, "null argument");
+  KMCHK(counter_sketch_settled(c));
   if (!c->finished) return fail(KM_E_STATE, "km_counter_finish comes first");
   *n = c->n_out;
   if (!keys && !counts) return KM_OK;

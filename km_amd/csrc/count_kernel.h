@@ -27,8 +27,11 @@ constexpr uint32_t COUNT_PAD = 128;     // readable bytes behind a staged chunk 
 // (CM_ALLT_HAVE / CM_ALLT_MATCH: setops_kernel.h's "claimed" and spare word of the key ~0, which has no slot;
 //  filter_kernel.h: CM_ALLT_HAVE = the key ~0 is in the filter)
 // (CM_HITS: filter_kernel.h's tally of the windows whose key was in the filter)
+// (CM_NOTED / CM_ADMITTED: sketch_kernel.h's tallies of the windows noted in pass 1 and counted in pass 2;
+//  CM_BITS_1 / CM_BITS_2: the set bits of the sketch's two planes, k_sketch_fill)
 enum { CM_DISTINCT = 0, CM_BASES = 1, CM_KMERS = 2, CM_ALLT = 3, CM_ERROR = 4, CM_OUT = 5, CM_FORMAT = 6, CM_RECORDS = 7,
-       CM_ALLT_HAVE = 8, CM_ALLT_MATCH = 9, CM_HITS = 10, CM_WORDS = 11 };
+       CM_ALLT_HAVE = 8, CM_ALLT_MATCH = 9, CM_HITS = 10, CM_NOTED = 11, CM_ADMITTED = 12, CM_BITS_1 = 13, CM_BITS_2 = 14,
+       CM_WORDS = 15 };
 
 __global__ void k_count_init(CountSlot* slots, uint64_t n_slots) {
   uint4* p = reinterpret_cast<uint4*>(slots);

@@ -43,6 +43,7 @@ extern "C" int km_counter_set_filter(km_counter_t* c, const uint64_t* keys, uint
   if (!c || (n && !keys)) return fail(KM_E_ARG, "null argument");
   KMCHK(counter_usable(c));
   if (c->filter_tier) return fail(KM_E_STATE, "counter already has a filter");
+  if (c->sketch_pass) return fail(KM_E_STATE, "counter has a sketch: it takes no filter");
   if (c->feed != FEED_NONE) return fail(KM_E_STATE, "counter has been fed: the filter comes before the first add_* or set_* call");
   if (n >> 60) return fail(KM_E_ARG, "%llu filter keys: too many", (unsigned long long)n);
   if (c->k < 32)

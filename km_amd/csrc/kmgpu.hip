@@ -29,6 +29,9 @@
 //                  pairs (select_host.h's SelDev per mate, a Staging in and a TextDrain out per mate)
 //   filter_host.h  km_counter_set_filter, km_counter_filter_stats: a counter that counts only a given set of k-mers
 //                  (the seed of its table; launch_filtered, which count_host.h's launch_insert calls)
+//   sketch_host.h  km_sketch_words, km_sketch_slot, km_counter_set_sketch, km_counter_sketch_done,
+//                  km_counter_sketch_stats: a counter fed twice, whose table takes only the k-mers a first pass saw
+//                  again (launch_sketch, which count_host.h's launch_insert calls)
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.
 #include <hip/hip_runtime.h>
@@ -76,7 +79,8 @@
 #include "select_rule.h"
 #include "select_pair_kernel.h"
 #include "select_pair_rule.h"
-#include "filter_kernel.h"      // (last: every kernel before it keeps its place in the code object)
+#include "filter_kernel.h"      // (behind those above: every kernel before it keeps its place in the code object)
+#include "sketch_kernel.h"      // (last, for the same reason)
 
 using namespace kmd;
 
@@ -95,4 +99,5 @@ using namespace kmd;
 #include "scan_host.h"
 #include "select_host.h"
 #include "select_pair_host.h"
-#include "filter_host.h"        // (last: k_count_filtered's two instances enter the code object behind all others)
+#include "filter_host.h"        // (k_count_filtered's two instances enter the code object behind all others)
+#include "sketch_host.h"        // (last: it uses filter_host.h's grid cap)

@@ -46,6 +46,7 @@ SYMBOLS = [
     "km_jf_file_info", "km_counter_add_records", "km_counter_add_jf", "km_counter_merge_stats",
     "km_counter_set_records", "km_counter_set_jf", "km_counter_finish_range",
     "km_counter_set_filter", "km_counter_filter_stats",
+    "km_sketch_words", "km_sketch_slot", "km_counter_set_sketch", "km_counter_sketch_done", "km_counter_sketch_stats",
     "km_histo_layout", "km_counter_histo", "km_jf_histo", "km_histo_kernel_ms", "km_histo_text", "km_histo_stats_text",
     "km_dump_text", "km_jf_dump", "km_counter_dump", "kmjf_query_text", "km_dump_kernel_ms",
     "kmjf_cov_seqs", "kmjf_scan_text", "km_scan_kernel_ms",
@@ -321,6 +322,12 @@ def load():
         "km_counter_finish_range": [vp, u32, u32, C.POINTER(vp)],
         "km_counter_set_filter": [vp, vp, u64],
         "km_counter_filter_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64),
+                                    C.POINTER(C.c_float)],
+        "km_sketch_words": [u64, C.POINTER(u64)],
+        "km_sketch_slot": [u64, u64, C.POINTER(u64), C.POINTER(u32)],
+        "km_counter_set_sketch": [vp, u64],
+        "km_counter_sketch_done": [vp],
+        "km_counter_sketch_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64),
                                     C.POINTER(C.c_float)],
         "km_histo_layout": [u64, u64, u64, C.POINTER(u64), C.POINTER(u64)],
         "km_counter_histo": [vp, u64, u64, u64, u32, u32, vp, u64, C.POINTER(HistoStats)],
@@ -616,6 +623,22 @@ def fastq_cut(data):
     return int(cut.value)
 
 
+def sketch_words(expected_distinct):
+    """km_sketch_words: the size, in 64-bit words, of Counter.set_sketch's sketch for that many expected distinct
+    k-mers: the smallest power of two >= max(64, ceil(n / 2)).  Host only."""
+    words = C.c_uint64()
+    check(load().km_sketch_words(int(expected_distinct), C.byref(words)))
+    return int(words.value)
+
+
+def sketch_slot(key, words):
+    """km_sketch_slot: (word index, 32-bit mask of one to three bits) of `key` in a sketch of `words` words
+    (include/kmgpu.h has the rule).  Host only."""
+    word, mask = C.c_uint64(), C.c_uint32()
+    check(load().km_sketch_slot(int(key), int(words), C.byref(word), C.byref(mask)))
+    return int(word.value), int(mask.value)
+
+
 def _qual_byte(min_qual_char):
     """0..255 from an int, or from a str / bytes of one character."""
     if isinstance(min_qual_char, str):
@@ -719,6 +742,33 @@ class Counter(_Handle):
                                                 C.byref(ms)))
         return {"n_keys": int(n.value), "kmers_hit": int(hit.value), "tier": FILTER_TIERS[tier.value],
                 "lds_keys": int(cap.value), "kernel_ms": float(ms.value)}
+
+    def set_sketch(self, words):
+        """km_counter_set_sketch: the counter is fed twice from now on.  What is fed until sketch_done() is only noted
+        in a two-plane Bloom sketch of `words` 64-bit words (a power of two, 64 .. 2^40; sketch_words(n) sizes it for n
+        expected distinct k-mers); what is fed afterwards is counted only if the sketch saw its k-mer at least twice in
+        the first pass, or falsely says so.  With both passes over the same reads, finish(2) gives exactly the records
+        of a plain counter while the table holds the admitted k-mers alone.  Once, before anything has been fed, and
+        not beside a filter.  This project's own semantics (what `jellyfish bc` + `count --bc` are for)."""
+        check(self._lib.km_counter_set_sketch(self._c, int(words)))
+
+    def sketch_done(self):
+        """km_counter_sketch_done: ends the first pass (waits for it; a malformed FASTQ record of that pass raises
+        here at the latest).  The next add_* call starts a fresh stream."""
+        check(self._lib.km_counter_sketch_done(self._c))
+
+    def sketch_stats(self):
+        """km_counter_sketch_stats (waits for everything added so far): dict(words, bits_1 / bits_2 = set bits of the
+        planes "seen" / "seen again", kmers_noted = windows of the first pass, kmers_admitted = windows the second pass
+        counted, note_ms / count_ms = the time of the kernels of either pass, needs KM_COUNT_TIME_FILTER=1 when the
+        counter is made)."""
+        w, b1, b2, noted, adm = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        ms = (C.c_float * 2)()
+        check(self._lib.km_counter_sketch_stats(self._c, C.byref(w), C.byref(b1), C.byref(b2), C.byref(noted),
+                                                C.byref(adm), ms))
+        return {"words": int(w.value), "bits_1": int(b1.value), "bits_2": int(b2.value),
+                "kmers_noted": int(noted.value), "kmers_admitted": int(adm.value), "note_ms": float(ms[0]),
+                "count_ms": float(ms[1])}
 
     def merge_stats(self):
         """km_counter_merge_stats (waits for everything added so far): dict(records_in = records with count > 0

@@ -1,5 +1,6 @@
 // count_host.h — km_counter_*, km_text_strip, km_fastq_cut (host part of kmgpu.hip; device side: count_kernel.h,
-// fastq_kernel.h; host helpers: fastx_strip.h, fastq_cut.h; records of existing tables: merge_host.h)
+// fastq_kernel.h, and filter_kernel.h / sketch_kernel.h for the counter's other modes, all launched by launch_insert;
+// host helpers: fastx_strip.h, fastq_cut.h; records of existing tables: merge_host.h)
 // ------------------------------------------------------------------ counting k-mers from reads
 // km_counter (include/kmgpu.h): text or bases are staged in two pinned buffers that take turns,
 // copied and inserted (count_kernel.h) on the counter's own stream, so the host strips the next block while the
@@ -36,6 +37,11 @@ const char* fastq_error_text(unsigned kind) {
 // What a counter has been fed: text, FASTQ and sum / max records (plain), or the inputs of one set operation.
 enum { FEED_NONE = 0, FEED_PLAIN = 1, FEED_SET = 2 };
 
+// What a counter does with the windows of its text, i.e. which kernel launch_insert launches: every key inserted; only
+// the keys of a filter counted, probed in LDS or in HBM (filter_host.h); or, with a sketch (sketch_host.h), every key
+// noted in the first pass and the admitted ones inserted in the second.
+enum CountMode { COUNT_PLAIN = 0, COUNT_FILTER_LDS, COUNT_FILTER_HBM, COUNT_SKETCH_NOTE, COUNT_SKETCH_COUNT };
+
 struct km_counter {
   int device = 0, k = 0, canonical = 0;
   Stream st;                              // (declared first: destroyed last)
@@ -59,13 +65,11 @@ struct km_counter {
   int feed = FEED_NONE;                   // what the counter has taken: the two kinds do not mix (setops_host.h)
   int set_op = 0;                         // FEED_SET: KM_SET_INTERSECT / KM_SET_SUBTRACT
   uint32_t set_inputs = 0;                // FEED_SET: inputs so far, the empty ones too
-  int filter_tier = 0;                    // filter_host.h: 0 no filter, 1 the LDS tier, 2 the HBM tier
-  uint32_t filter_blocks = 0;             // ... the most blocks of a filtered launch
+  CountMode mode = COUNT_PLAIN;           // set by km_counter_set_filter, km_counter_set_sketch, km_counter_sketch_done
+  uint32_t grid_cap = 0;                  // the most blocks of a launch with a bounded grid (filtered, noting)
   KernelSpans insert_spans;               // KM_COUNT_TIME_FILTER: around every insert launch, filtered or not
-  int sketch_pass = 0;                    // sketch_host.h: 0 no sketch, 1 the noting pass, 2 the counting pass
-  DevBuf<uint64_t> sketch;                // ... its words (sketch_rule.h)
+  DevBuf<uint64_t> sketch;                // sketch_host.h: the words of the sketch (sketch_rule.h)
   uint64_t sketch_words = 0;
-  uint32_t sketch_blocks = 0;             // ... the most blocks of a noting launch
   float sketch_note_ms = 0.f;             // ... what insert_spans held when the noting pass ended
   DevBuf<uint64_t> out_keys;
   DevBuf<uint32_t> out_counts;
@@ -98,12 +102,15 @@ static int counter_takes_plain(const km_counter* c) {
   return KM_OK;
 }
 
+static bool counter_has_filter(const km_counter* c) { return c->mode == COUNT_FILTER_LDS || c->mode == COUNT_FILTER_HBM; }
+static bool counter_has_sketch(const km_counter* c) { return c->mode == COUNT_SKETCH_NOTE || c->mode == COUNT_SKETCH_COUNT; }
+
 // ... and every call that feeds records, of either kind: a filter restricts what is counted from reads, and a
 // record brings a count of its own (filter_host.h)
 static int counter_takes_records(const km_counter* c) {
-  if (c->filter_tier)
+  if (counter_has_filter(c))
     return fail(KM_E_STATE, "counter has a filter: it counts reads (add_bases, add_text, add_fastq) and takes no records");
-  if (c->sketch_pass)
+  if (counter_has_sketch(c))
     return fail(KM_E_STATE, "counter has a sketch: it counts reads (add_bases, add_text, add_fastq) and takes no records");
   return KM_OK;
 }
@@ -111,12 +118,12 @@ static int counter_takes_records(const km_counter* c) {
 // ... and every call that reads the table or ends the counter: while a sketch is in its noting pass there is no table
 // to speak of (sketch_host.h)
 static int counter_sketch_settled(const km_counter* c) {
-  if (c->sketch_pass == 1) return fail(KM_E_STATE, "the counter's sketch is in its first pass: km_counter_sketch_done comes first");
+  if (c->mode == COUNT_SKETCH_NOTE) return fail(KM_E_STATE, "the counter's sketch is in its first pass: km_counter_sketch_done comes first");
   return KM_OK;
 }
 
 // nothing claims a slot: a filter's table never grows, and the noting pass of a sketch does not touch the table
-static bool counter_table_fixed(const km_counter* c) { return c->filter_tier || c->sketch_pass == 1; }
+static bool counter_table_fixed(const km_counter* c) { return counter_has_filter(c) || c->mode == COUNT_SKETCH_NOTE; }
 
 // waits for everything enqueued
 static int counter_read_meta(km_counter* c, unsigned long long* m) {
@@ -169,25 +176,41 @@ static int counter_reserve(km_counter* c, uint64_t windows) {
   return KM_OK;
 }
 
-static void launch_filtered(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from);   // filter_host.h
-static void launch_sketch(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from);     // sketch_host.h
-
 // text[0 .. n) on the device into the table; the windows that start before own_from belong to the piece before.
-// A counter with a filter only looks its keys up (filter_kernel.h); one with a sketch notes the keys in its first pass
-// and counts the admitted ones in its second (sketch_kernel.h).
+// A lane per 32 bytes, 256 lanes per block.  A counter with a filter only looks its keys up (filter_kernel.h); one with
+// a sketch notes the keys in its first pass and counts the admitted ones in its second (sketch_kernel.h).  The filtered
+// and the noting kernel take a bounded grid: a block makes as many trips over the text as it takes.
 static int launch_insert(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from) {
   const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
+  const dim3 block(256), full((uint32_t)((lanes + 255) / 256)), capped(std::min(full.x, c->grid_cap));
+  const uint32_t shift = 64u - kmsketch::log2_words(c->sketch_words);      // (of a sketch; unused otherwise)
   KMCHK(c->insert_spans.open(c->st));
-  if (c->filter_tier)
-    launch_filtered(c, text, n, own_from);
-  else if (c->sketch_pass)
-    launch_sketch(c, text, n, own_from);
-  else
-    hipLaunchKernelGGL(k_count_insert, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, c->st, text, n, own_from,
-                       c->k, c->canonical, c->table.p, c->slots - 1, c->meta.p);
+  switch (c->mode) {
+    case COUNT_PLAIN:
+      hipLaunchKernelGGL(k_count_insert, full, block, 0, c->st, text, n, own_from, c->k, c->canonical, c->table.p,
+                         c->slots - 1, c->meta.p);
+      break;
+    case COUNT_FILTER_LDS:
+      hipLaunchKernelGGL(k_count_filtered<true>, capped, block, 0, c->st, text, n, own_from, c->k, c->canonical,
+                         c->table.p, c->slots - 1, c->meta.p);
+      break;
+    case COUNT_FILTER_HBM:
+      hipLaunchKernelGGL(k_count_filtered<false>, capped, block, 0, c->st, text, n, own_from, c->k, c->canonical,
+                         c->table.p, c->slots - 1, c->meta.p);
+      break;
+    case COUNT_SKETCH_NOTE:
+      hipLaunchKernelGGL(k_sketch_note, capped, block, 0, c->st, text, n, own_from, c->k, c->canonical, c->sketch.p,
+                         shift, c->meta.p);
+      break;
+    case COUNT_SKETCH_COUNT:
+      hipLaunchKernelGGL(k_count_solid, full, block, 0, c->st, text, n, own_from, c->k, c->canonical, c->table.p,
+                         c->slots - 1, c->sketch.p, shift, c->meta.p);
+      break;
+  }
   HIPCHK(hipGetLastError());
   return c->insert_spans.close(c->st);
 }
+static_assert(FILTER_THREADS == 256 && SKETCH_THREADS == 256, "launch_insert: one block size for the five kernels");
 
 // Enqueue the piece of add_bases / add_text (copy + insert) and turn to the other buffer, which starts with the
 // last k - 1 bytes of this one.  Nothing to do while the buffer holds only such carried bytes.
@@ -473,7 +496,7 @@ static int counter_finish_cut(km_counter* c, uint32_t lower_count, uint32_t uppe
   if (n > m[CM_DISTINCT]) return fail(KM_E_HIP, "compaction wrote %llu records for %llu keys", m[CM_OUT], m[CM_DISTINCT]);
   // T^32 of a non-canonical k = 32 table (count_kernel.h; under a set operation its cells are those of setops_kernel.h,
   // and a filter that holds it lists it with whatever count it has, 0 too)
-  const bool have = intersect || c->filter_tier ? m[CM_ALLT_HAVE] != 0 : m[CM_ALLT] != 0;
+  const bool have = intersect || counter_has_filter(c) ? m[CM_ALLT_HAVE] != 0 : m[CM_ALLT] != 0;
   const uint32_t allt = intersect ? ~(uint32_t)m[CM_ALLT] : (uint32_t)std::min<unsigned long long>(m[CM_ALLT], 0xFFFFFFFFull);
   if (have && m[CM_ALLT_MATCH] == want && allt >= lower_count && allt <= upper_count) {
     const uint64_t key = EMPTY;

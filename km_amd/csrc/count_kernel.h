@@ -1,5 +1,7 @@
 // count_kernel.h — counting k-mers from reads: a counting hash table in HBM and the three kernels that fill it,
-// grow it and empty it into the record arrays kmjf_upload_from_device takes.
+// grow it and empty it into the record arrays kmjf_upload_from_device takes.  How a lane walks the
+// text is count_rule.h's; count_lane here loads its 64 bytes, for this kernel and for those of filter_kernel.h and
+// sketch_kernel.h.
 //
 // Table: open addressing with linear probing over 16-byte slots {u64 key, u32 count, u32 unused}; the key and
 // its count share one 16-byte piece of a line, so the add that follows a key's lookup hits the line that lookup
@@ -8,6 +10,7 @@
 // Counts are integers added with atomics: the final set of (key, count) does not depend on arrival order.
 // The slot's fourth word is 0 everywhere except under the set operations of setops_kernel.h.
 #pragma once
+#include "count_rule.h"
 #include "device_common.h"
 
 namespace kmd {
@@ -19,8 +22,8 @@ struct __attribute__((aligned(16))) CountSlot {
 };
 static_assert(sizeof(CountSlot) == 16, "one dwordx4 per slot");
 
-constexpr uint32_t COUNT_RUN = 32;      // window start positions a lane owns
-constexpr uint32_t COUNT_PAD = 128;     // readable bytes behind a staged chunk (the last lane loads 64 from its start)
+constexpr uint32_t COUNT_RUN = kmcount::RUN;      // window start positions a lane owns
+constexpr uint32_t COUNT_PAD = kmcount::PAD;      // readable bytes behind a staged chunk (the last lane loads 64 from its start)
 // cells of the counter's device meta block (u64 each)
 // (CM_FORMAT: fastq_kernel.h's smallest (stream offset << 8 | kind), ~0 while the text is well-formed)
 // (CM_RECORDS: merge_kernel.h's tally of the records taken; CM_BASES / CM_KMERS tally text only)
@@ -74,57 +77,36 @@ __device__ inline void wave_add(unsigned long long* cell, uint32_t v) {
   if (lane_id() == 0 && v) atomicAdd(cell, (unsigned long long)v);
 }
 
-// text[0 .. n): bases (ACGTacgt) and breaks (any other byte).  Lane g owns the window starts
-// [32 g, 32 g + 32): it loads the 64 bytes from 32 g as four aligned dwordx4 (its own 32 and k - 1 <= 31 of its
-// neighbour's), rolls the forward and the reverse-complement key over them with a count of the bases since
-// the last break, and inserts every window of k bases that starts in its own range and ends before n.
-// own_from: bytes [0, own_from) were counted as bases by the piece before (pieces of one call overlap by k - 1).
+// The walk of one lane (count_rule.h: kmcount::lane_walk) over the 64 bytes from text + s, loaded as four aligned
+// dwordx4; s = 32 * the lane's index, s < n.  The four counting kernels (k_count_insert here, k_count_filtered,
+// k_sketch_note, k_count_solid) are each a distribution of lanes and a functor given to this.
+template <class Window>
+__device__ inline uint32_t count_lane(const uint8_t* text, uint64_t n, uint64_t s, uint32_t own_from, int k, int canonical,
+                                      uint32_t& bases, uint32_t& kmers, Window window) {
+  const uint4* p = reinterpret_cast<const uint4*>(text + s);
+  const uint4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+  const uint32_t w[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w,
+                          q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
+  return kmcount::lane_walk(w, n, s, own_from, k, canonical, bases, kmers, window);
+}
+
+// text[0 .. n): bases and breaks, PAD readable bytes behind them; own_from: bytes [0, own_from) were counted as bases
+// by the piece before (count_rule.h).  One lane per thread; every window's key is inserted with count 1, the key ~0
+// tallied in CM_ALLT instead.
 __global__ __launch_bounds__(256) void k_count_insert(const uint8_t* text, uint64_t n, uint32_t own_from, int k,
                                                       int canonical, CountSlot* tab, uint64_t smask,
                                                       unsigned long long* meta) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t s = g * COUNT_RUN;
-  uint32_t claimed = 0, bases = 0, kmers = 0, allt = 0;
-  if (s < n) {
-    const uint4* p = reinterpret_cast<const uint4*>(text + s);
-    const uint4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-    const uint32_t w[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w,
-                            q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
-    const uint64_t kmask = k >= 32 ? ~0ull : ((1ull << (2 * k)) - 1);
-    const uint32_t rshift = 2u * (uint32_t)(k - 1);
-    const uint32_t jend = (uint32_t)k + COUNT_RUN - 1;        // bytes this lane looks at (<= 63)
-    uint64_t fwd = 0, rev = 0;
-    uint32_t run = 0;
-#pragma unroll
-    for (uint32_t d = 0; d < 16; ++d) {
-      if (4 * d < jend) {
-        const uint32_t word = w[d];
-#pragma unroll 1
-        for (uint32_t b = 0; b < 4; ++b) {
-          const uint32_t j = 4 * d + b;
-          const uint32_t ch = (word >> (8 * b)) & 0xFFu;
-          const uint32_t up = ch & 0xDFu;
-          const bool base = (up == 'A' || up == 'C' || up == 'G' || up == 'T') && s + j < n && j < jend;
-          uint32_t c = (ch >> 1) & 3u;                         // A 0, C 1, T 2, G 3
-          c ^= c >> 1;                                         // A 0, C 1, G 2, T 3
-          fwd = ((fwd << 2) | c) & kmask;
-          rev = (rev >> 2) | ((uint64_t)(3u - c) << rshift);
-          run = base ? run + 1 : 0;
-          bases += (base && j < COUNT_RUN && s + j >= own_from) ? 1u : 0u;
-          if (run >= (uint32_t)k) {                            // (j < jend: the window starts at j - k + 1 < 32)
-            const uint64_t key = (canonical && rev < fwd) ? rev : fwd;
-            ++kmers;
-            if (key == EMPTY) ++allt;
-            else claimed += count_add(tab, smask, key, 1u, meta);
-          }
-        }
-      }
-    }
-  }
-  wave_add(&meta[CM_DISTINCT], claimed);
+  const uint64_t s = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * COUNT_RUN;
+  uint32_t bases = 0, kmers = 0, tally = 0;              // tally: claimed | allt << 8 (each <= 32)
+  if (s < n)
+    tally = count_lane(text, n, s, own_from, k, canonical, bases, kmers, [=](uint64_t key) {
+      if (key == EMPTY) return 1u << 8;
+      return count_add(tab, smask, key, 1u, meta);
+    });
+  wave_add(&meta[CM_DISTINCT], tally & 0xFFu);
   wave_add(&meta[CM_BASES], bases);
   wave_add(&meta[CM_KMERS], kmers);
-  wave_add(&meta[CM_ALLT], allt);
+  wave_add(&meta[CM_ALLT], tally >> 8);
 }
 
 // Every occupied slot of the old table into the new one (twice the capacity or more), its count added.

@@ -1,5 +1,6 @@
 // filter_host.h — km_counter_set_filter, km_counter_filter_stats (host part of kmgpu.hip; device side: filter_kernel.h;
-// where a filtered counter differs on its way through count_host.h: launch_insert, counter_flush, fastq_enqueue)
+// where a filtered counter differs on its way through count_host.h: its CountMode in launch_insert, counter_table_fixed
+// in counter_flush and fastq_enqueue)
 // ------------------------------------------------------------------ counting only a given set of k-mers
 // The filter replaces the counter's table by one that holds exactly the filter's keys, each with count 0, at the
 // smallest power of two >= max(64, 2 * distinct) slots.  How many keys are distinct is known only once the device has
@@ -13,37 +14,26 @@ uint64_t filter_slots_for(uint64_t distinct) {
   return s;
 }
 
-// KM_COUNT_FILTER_BLOCKS, or what fills the device: the LDS tier's 64 KiB let two blocks share a CU's 160 KiB, the
-// HBM tier's blocks are bounded by their waves alone (eight of four waves each).
-int filter_grid_cap(int device, int tier, uint32_t* blocks) {
+// The most blocks of a bounded grid (km_counter::grid_cap): KM_COUNT_FILTER_BLOCKS, or what fills the device.  The LDS
+// tier's 64 KiB let two blocks share a CU's 160 KiB; the HBM tier's blocks, and those of a sketch's noting pass, are
+// bounded by their waves alone (eight of four waves each).
+int filter_grid_cap(int device, CountMode mode, uint32_t* blocks) {
   if (const char* e = getenv("KM_COUNT_FILTER_BLOCKS")) {
     const unsigned long long v = strtoull(e, nullptr, 10);
     if (v) { *blocks = (uint32_t)std::min<unsigned long long>(v, 1u << 20); return KM_OK; }
   }
   int cus = 0;
   HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  *blocks = (uint32_t)std::max(cus, 1) * (tier == 1 ? 2u : 8u);
+  *blocks = (uint32_t)std::max(cus, 1) * (mode == COUNT_FILTER_LDS ? 2u : 8u);
   return KM_OK;
 }
 }  // namespace
 
-// (count_host.h: launch_insert)  A bounded grid: a block makes as many trips over the text as it takes.
-static void launch_filtered(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from) {
-  const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
-  const uint32_t grid = (uint32_t)std::min<uint64_t>((lanes + FILTER_THREADS - 1) / FILTER_THREADS, c->filter_blocks);
-  if (c->filter_tier == 1)
-    hipLaunchKernelGGL(k_count_filtered<true>, dim3(grid), dim3(FILTER_THREADS), 0, c->st, text, n, own_from, c->k,
-                       c->canonical, c->table.p, c->slots - 1, c->meta.p);
-  else
-    hipLaunchKernelGGL(k_count_filtered<false>, dim3(grid), dim3(FILTER_THREADS), 0, c->st, text, n, own_from, c->k,
-                       c->canonical, c->table.p, c->slots - 1, c->meta.p);
-}
-
 extern "C" int km_counter_set_filter(km_counter_t* c, const uint64_t* keys, uint64_t n) {
   if (!c || (n && !keys)) return fail(KM_E_ARG, "null argument");
   KMCHK(counter_usable(c));
-  if (c->filter_tier) return fail(KM_E_STATE, "counter already has a filter");
-  if (c->sketch_pass) return fail(KM_E_STATE, "counter has a sketch: it takes no filter");
+  if (counter_has_filter(c)) return fail(KM_E_STATE, "counter already has a filter");
+  if (counter_has_sketch(c)) return fail(KM_E_STATE, "counter has a sketch: it takes no filter");
   if (c->feed != FEED_NONE) return fail(KM_E_STATE, "counter has been fed: the filter comes before the first add_* or set_* call");
   if (n >> 60) return fail(KM_E_ARG, "%llu filter keys: too many", (unsigned long long)n);
   if (c->k < 32)
@@ -76,15 +66,15 @@ extern "C" int km_counter_set_filter(km_counter_t* c, const uint64_t* keys, uint
     HIPCHK(hipStreamSynchronize(c->st));
     seeded = std::move(tight);
   }
-  int tier = slots <= FILTER_LDS_SLOTS ? 1 : 2;
+  CountMode mode = slots <= FILTER_LDS_SLOTS ? COUNT_FILTER_LDS : COUNT_FILTER_HBM;
   if (const char* e = getenv("KM_COUNT_FILTER_LDS"))
-    if (atoi(e) == 0) tier = 2;
-  KMCHK(filter_grid_cap(c->device, tier, &c->filter_blocks));
+    if (atoi(e) == 0) mode = COUNT_FILTER_HBM;
+  KMCHK(filter_grid_cap(c->device, mode, &c->grid_cap));
   c->table = std::move(seeded);
   c->slots = slots;
   c->occ_ub = m[CM_DISTINCT];
   c->last.slots = slots;
-  c->filter_tier = tier;
+  c->mode = mode;
   return KM_OK;
 }
 
@@ -98,9 +88,9 @@ extern "C" int km_counter_filter_stats(km_counter_t* c, uint64_t* n_keys, uint64
   KMCHK(counter_read_meta(c, m));
   float ms = 0.f;
   KMCHK(c->insert_spans.drain(&ms));
-  if (n_keys) *n_keys = c->filter_tier ? c->last.distinct : 0;
+  if (n_keys) *n_keys = counter_has_filter(c) ? c->last.distinct : 0;
   if (kmers_hit) *kmers_hit = m[CM_HITS];
-  if (tier) *tier = c->filter_tier;
+  if (tier) *tier = c->mode == COUNT_FILTER_LDS ? 1 : c->mode == COUNT_FILTER_HBM ? 2 : 0;
   if (lds_keys) *lds_keys = FILTER_LDS_SLOTS / 2;
   if (kernel_ms) *kernel_ms = ms;
   return KM_OK;

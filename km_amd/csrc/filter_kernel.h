@@ -53,11 +53,10 @@ __device__ inline uint64_t filter_lookup_lds(const uint64_t* lkeys, uint64_t sma
   return NO_SLOT;
 }
 
-// text, n, own_from, k, canonical as for k_count_insert, and its walk over a lane's 64 bytes: 32 own window starts,
-// k - 1 bytes of the neighbour, a break at any byte that is no base or lies at or behind n.  Lane g of trip t owns the
-// starts [32 (g + t * lanes of the grid), + 32).  A window adds 1 to its key's count only if the key is in the table;
-// the key ~0 goes to CM_ALLT only if the filter holds it (CM_ALLT_HAVE).  CM_BASES / CM_KMERS tally all bases and all
-// windows as k_count_insert does, CM_HITS the windows that were counted.
+// text, n, own_from, k, canonical as for k_count_insert, and the same walk of a lane (count_kernel.h: count_lane).
+// A bounded grid: lane g of trip t owns the starts [32 (g + t * lanes of the grid), + 32).  A window adds 1 to its
+// key's count only if the key is in the table; the key ~0 goes to CM_ALLT only if the filter holds it (CM_ALLT_HAVE).
+// CM_BASES / CM_KMERS tally all bases and all windows as k_count_insert does, CM_HITS the windows that were counted.
 template <bool LDS>
 __global__ __launch_bounds__(256) void k_count_filtered(const uint8_t* text, uint64_t n, uint32_t own_from, int k,
                                                         int canonical, CountSlot* tab, uint64_t smask,
@@ -72,51 +71,20 @@ __global__ __launch_bounds__(256) void k_count_filtered(const uint8_t* text, uin
     __syncthreads();
   }
   const bool allt_have = meta[CM_ALLT_HAVE] != 0;     // (written by the seed, long before this launch)
-  const uint64_t kmask = k >= 32 ? ~0ull : ((1ull << (2 * k)) - 1);
-  const uint32_t rshift = 2u * (uint32_t)(k - 1);
-  const uint32_t jend = (uint32_t)k + COUNT_RUN - 1;   // bytes a lane looks at (<= 63)
+  const uint64_t* keys = lkeys;
   uint32_t bases = 0, kmers = 0, allt = 0, hits = 0;
   for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g * COUNT_RUN < n;
        g += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t s = g * COUNT_RUN;
-    const uint4* p = reinterpret_cast<const uint4*>(text + s);
-    const uint4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-    const uint32_t w[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w,
-                            q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
-    uint64_t fwd = 0, rev = 0;
-    uint32_t run = 0;
-#pragma unroll
-    for (uint32_t d = 0; d < 16; ++d) {
-      if (4 * d < jend) {
-        const uint32_t word = w[d];
-#pragma unroll 1
-        for (uint32_t b = 0; b < 4; ++b) {
-          const uint32_t j = 4 * d + b;
-          const uint32_t ch = (word >> (8 * b)) & 0xFFu;
-          const uint32_t up = ch & 0xDFu;
-          const bool base = (up == 'A' || up == 'C' || up == 'G' || up == 'T') && s + j < n && j < jend;
-          uint32_t c = (ch >> 1) & 3u;                         // A 0, C 1, T 2, G 3
-          c ^= c >> 1;                                         // A 0, C 1, G 2, T 3
-          fwd = ((fwd << 2) | c) & kmask;
-          rev = (rev >> 2) | ((uint64_t)(3u - c) << rshift);
-          run = base ? run + 1 : 0;
-          bases += (base && j < COUNT_RUN && s + j >= own_from) ? 1u : 0u;
-          if (run >= (uint32_t)k) {                            // (j < jend: the window starts at j - k + 1 < 32)
-            const uint64_t key = (canonical && rev < fwd) ? rev : fwd;
-            ++kmers;
-            if (key == EMPTY) {
-              if (allt_have) { ++allt; ++hits; }
-            } else {
-              const uint64_t idx = LDS ? filter_lookup_lds(lkeys, smask, key, meta) : count_lookup(tab, smask, key, meta);
-              if (idx != NO_SLOT) {
-                atomicAdd(&tab[idx].count, 1u);
-                ++hits;
-              }
-            }
-          }
-        }
-      }
-    }
+    // hits | allt << 16 of this trip (each <= 32; unpacked per trip: a block may make thousands of them)
+    const uint32_t tally = count_lane(text, n, g * COUNT_RUN, own_from, k, canonical, bases, kmers, [=](uint64_t key) {
+      if (key == EMPTY) return allt_have ? (1u << 16) | 1u : 0u;
+      const uint64_t idx = LDS ? filter_lookup_lds(keys, smask, key, meta) : count_lookup(tab, smask, key, meta);
+      if (idx == NO_SLOT) return 0u;
+      atomicAdd(&tab[idx].count, 1u);
+      return 1u;
+    });
+    hits += tally & 0xFFFFu;
+    allt += tally >> 16;
   }
   wave_add(&meta[CM_BASES], bases);
   wave_add(&meta[CM_KMERS], kmers);

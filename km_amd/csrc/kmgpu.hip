@@ -11,7 +11,8 @@
 //   result_host.h  reading a delivered step: km_batch_result / _pump / _fetch, diagnostics and measurement exports
 //   kmin_host.h    km_linear_kmin
 //   count_host.h   km_counter_*, km_text_strip, km_fastq_cut; the one way of text, FASTQ and record pieces through the
-//                  counter's Staging (claim, counter_reserve, ship; counter_begin_pieces)
+//                  counter's Staging (claim, counter_reserve, ship; counter_begin_pieces); the counter's mode (plain,
+//                  filter in LDS / in HBM, sketch noting / counting) and launch_insert, the one switch over it
 //   jf_order_host.h  km_jf_*, km_counter_write_jf: files in Jellyfish's own record order (out through the same Staging)
 //   merge_host.h   km_jf_file_info, km_counter_add_records, km_counter_add_jf: records of existing tables, as pieces
 //                  on the counter's staging
@@ -28,12 +29,15 @@
 //   select_pair_host.h  km_select_pair_*: the same for the two mate streams of a paired-end run, kept or dropped as
 //                  pairs (select_host.h's SelDev per mate, a Staging in and a TextDrain out per mate)
 //   filter_host.h  km_counter_set_filter, km_counter_filter_stats: a counter that counts only a given set of k-mers
-//                  (the seed of its table; launch_filtered, which count_host.h's launch_insert calls)
+//                  (the seed of its table, the tier and the cap of its bounded grid)
 //   sketch_host.h  km_sketch_words, km_sketch_slot, km_counter_set_sketch, km_counter_sketch_done,
 //                  km_counter_sketch_stats: a counter fed twice, whose table takes only the k-mers a first pass saw
-//                  again (launch_sketch, which count_host.h's launch_insert calls)
+//                  again (the sketch, the end of its first pass, its statistics)
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
-// first instantiates them, and the code object is compared byte for byte across host-only changes.
+// first instantiates them, and the code object is compared byte for byte across host-only changes.  The two instances
+// of k_count_filtered are instantiated by count_host.h's launch_insert since all counting kernels are launched from
+// that one switch: they moved from the end of the code object, behind dump_host.h's six k_dump_* instances, to in
+// front of those six (behind the walk kernels of batch_host.h).  No other kernel changed its place.
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <sys/mman.h>
@@ -99,5 +103,5 @@ using namespace kmd;
 #include "scan_host.h"
 #include "select_host.h"
 #include "select_pair_host.h"
-#include "filter_host.h"        // (k_count_filtered's two instances enter the code object behind all others)
-#include "sketch_host.h"        // (last: it uses filter_host.h's grid cap)
+#include "filter_host.h"
+#include "sketch_host.h"        // (behind filter_host.h: it uses its grid cap)

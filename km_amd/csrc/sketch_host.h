@@ -1,26 +1,14 @@
 // sketch_host.h — km_sketch_words, km_sketch_slot, km_counter_set_sketch, km_counter_sketch_done,
 // km_counter_sketch_stats (host part of kmgpu.hip; device side: sketch_kernel.h; the rule: sketch_rule.h; where a counter
-// with a sketch differs on its way through count_host.h: launch_insert, counter_table_fixed, counter_sketch_settled)
+// with a sketch differs on its way through count_host.h: its CountMode in launch_insert, counter_table_fixed,
+// counter_sketch_settled)
 // ------------------------------------------------------------------ solid k-mers in two passes
-// A counter with a sketch is fed twice.  In the first pass (sketch_pass 1) the text takes its usual way through the
+// A counter with a sketch is fed twice.  In the first pass (COUNT_SKETCH_NOTE) the text takes its usual way through the
 // staging, and through the line table and mask of a FASTQ piece, but the kernel at the end of it notes every window's
 // key in the sketch and the table is neither touched nor grown.  km_counter_sketch_done ends that pass and makes the
-// counter's stream state that of a counter that has not been fed; from then on (sketch_pass 2) the kernel is the plain
+// counter's stream state that of a counter that has not been fed; from then on (COUNT_SKETCH_COUNT) the kernel is the plain
 // insert kernel with one more condition, and counter_reserve grows the table on its exact occupancy as always, which
 // now is that of the admitted keys.
-static void launch_sketch(km_counter* c, const uint8_t* text, uint64_t n, uint32_t own_from) {
-  const uint64_t lanes = (n + COUNT_RUN - 1) / COUNT_RUN;
-  const uint32_t shift = 64u - kmsketch::log2_words(c->sketch_words);
-  if (c->sketch_pass == 1) {
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((lanes + SKETCH_THREADS - 1) / SKETCH_THREADS, c->sketch_blocks);
-    hipLaunchKernelGGL(k_sketch_note, dim3(grid), dim3(SKETCH_THREADS), 0, c->st, text, n, own_from, c->k, c->canonical,
-                       c->sketch.p, shift, c->meta.p);
-  } else {
-    hipLaunchKernelGGL(k_count_solid, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, c->st, text, n, own_from, c->k,
-                       c->canonical, c->table.p, c->slots - 1, c->sketch.p, shift, c->meta.p);
-  }
-}
-
 // The set bits of the two planes into their meta cells (the caller reads the meta block next).
 static int sketch_fill(km_counter* c) {
   HIPCHK(hipMemsetAsync(c->meta.p + CM_BITS_1, 0, 16, c->st));       // CM_BITS_1 and CM_BITS_2 are neighbours
@@ -54,28 +42,28 @@ extern "C" int km_counter_set_sketch(km_counter_t* c, uint64_t words) {
   if (!kmsketch::words_valid(words))
     return fail(KM_E_ARG, "a sketch of %llu words: a power of two from 64 to 2^40 is needed", (unsigned long long)words);
   KMCHK(counter_usable(c));
-  if (c->sketch_pass) return fail(KM_E_STATE, "counter already has a sketch");
-  if (c->filter_tier) return fail(KM_E_STATE, "counter has a filter: it takes no sketch");
+  if (counter_has_sketch(c)) return fail(KM_E_STATE, "counter already has a sketch");
+  if (counter_has_filter(c)) return fail(KM_E_STATE, "counter has a filter: it takes no sketch");
   if (c->feed != FEED_NONE) return fail(KM_E_STATE, "counter has been fed: the sketch comes before the first add_* or set_* call");
   HIPCHK(hipSetDevice(c->device));
   DevBuf<uint64_t> sketch;
   uint32_t blocks = 0;
   KMCHK(sketch.alloc(words));
-  KMCHK(filter_grid_cap(c->device, 2, &blocks));        // (filter_host.h: eight blocks of four waves per CU)
+  KMCHK(filter_grid_cap(c->device, COUNT_SKETCH_NOTE, &blocks));   // (filter_host.h: eight blocks of four waves per CU)
   HIPCHK(hipMemsetAsync(sketch.p, 0, words * 8, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   c->sketch = std::move(sketch);
   c->sketch_words = words;
-  c->sketch_blocks = blocks;
-  c->sketch_pass = 1;
+  c->grid_cap = blocks;
+  c->mode = COUNT_SKETCH_NOTE;
   return KM_OK;
 }
 
 extern "C" int km_counter_sketch_done(km_counter_t* c) {
   if (!c) return fail(KM_E_ARG, "null argument");
   KMCHK(counter_usable(c));
-  if (c->sketch_pass == 0) return fail(KM_E_STATE, "counter has no sketch");
-  if (c->sketch_pass == 2) return fail(KM_E_STATE, "the sketch's first pass has ended already");
+  if (!counter_has_sketch(c)) return fail(KM_E_STATE, "counter has no sketch");
+  if (c->mode == COUNT_SKETCH_COUNT) return fail(KM_E_STATE, "the sketch's first pass has ended already");
   HIPCHK(hipSetDevice(c->device));
   KMCHK(counter_flush(c));
   KMCHK(sketch_fill(c));                                // (nothing writes the sketch from here on: the bits are final)
@@ -88,7 +76,7 @@ extern "C" int km_counter_sketch_done(km_counter_t* c) {
   c->fill = 0;
   c->own_from = 0;
   c->fq_offset = 0;
-  c->sketch_pass = 2;
+  c->mode = COUNT_SKETCH_COUNT;
   return KM_OK;
 }
 
@@ -98,7 +86,7 @@ extern "C" int km_counter_sketch_stats(km_counter_t* c, uint64_t* words, uint64_
   if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
   HIPCHK(hipSetDevice(c->device));
   if (!c->finished) KMCHK(counter_flush(c));
-  if (c->sketch_pass == 1) KMCHK(sketch_fill(c));
+  if (c->mode == COUNT_SKETCH_NOTE) KMCHK(sketch_fill(c));
   unsigned long long m[CM_WORDS];
   KMCHK(counter_read_meta(c, m));
   float ms = 0.f;
@@ -109,8 +97,8 @@ extern "C" int km_counter_sketch_stats(km_counter_t* c, uint64_t* words, uint64_
   if (kmers_noted) *kmers_noted = m[CM_NOTED];
   if (kmers_admitted) *kmers_admitted = m[CM_ADMITTED];
   if (kernel_ms) {
-    kernel_ms[0] = c->sketch_pass == 1 ? ms : c->sketch_note_ms;
-    kernel_ms[1] = c->sketch_pass == 2 ? ms : 0.f;
+    kernel_ms[0] = c->mode == COUNT_SKETCH_NOTE ? ms : c->sketch_note_ms;
+    kernel_ms[1] = c->mode == COUNT_SKETCH_COUNT ? ms : 0.f;
   }
   return KM_OK;
 }

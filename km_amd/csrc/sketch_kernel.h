@@ -4,8 +4,8 @@
 //   pass 1  k_sketch_note   every window's key is noted in the sketch; the counting table is not touched
 //   pass 2  k_count_solid   k_count_insert, but a window is counted only if the sketch admits its key
 //           k_sketch_fill   the set bits of either plane (statistics)
-// The three walk a lane's 64 bytes as k_count_insert does, through one template (count_lane_walk) that hands every
-// window's key to a functor.  Only vector loads, vector stores and vector atomics touch the sketch.
+// The two passes walk a lane's 64 bytes as k_count_insert does (count_kernel.h: count_lane), each with a functor of its
+// own.  Only vector loads, vector stores and vector atomics touch the sketch.
 #pragma once
 #include "count_kernel.h"
 #include "sketch_rule.h"
@@ -13,50 +13,6 @@
 namespace kmd {
 
 constexpr uint32_t SKETCH_THREADS = 256;
-
-// k_count_insert's walk of one lane: s = the lane's first byte (s < n), the 64 bytes from s as four aligned dwordx4
-// (its own 32 window starts and k - 1 <= 31 bytes of its neighbour's), forward and reverse-complement key rolled over
-// them with a count of the bases since the last break.  window(key) runs for every window of k bases that starts in
-// the lane's own range and ends before n, and the walk returns the sum of what it returned (at most 32 windows: a
-// functor may pack several tallies of a byte each); bases / kmers tally the lane's own bases at or behind own_from and
-// its windows.  The functor captures by value: a tally it took by reference would live in scratch.
-template <class Window>
-__device__ inline uint32_t count_lane_walk(const uint8_t* text, uint64_t n, uint64_t s, uint32_t own_from, int k,
-                                           int canonical, uint32_t& bases, uint32_t& kmers, Window window) {
-  const uint4* p = reinterpret_cast<const uint4*>(text + s);
-  const uint4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-  const uint32_t w[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w,
-                          q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
-  const uint64_t kmask = k >= 32 ? ~0ull : ((1ull << (2 * k)) - 1);
-  const uint32_t rshift = 2u * (uint32_t)(k - 1);
-  const uint32_t jend = (uint32_t)k + COUNT_RUN - 1;          // bytes this lane looks at (<= 63)
-  uint64_t fwd = 0, rev = 0;
-  uint32_t run = 0, sum = 0;
-#pragma unroll
-  for (uint32_t d = 0; d < 16; ++d) {
-    if (4 * d < jend) {
-      const uint32_t word = w[d];
-#pragma unroll 1
-      for (uint32_t b = 0; b < 4; ++b) {
-        const uint32_t j = 4 * d + b;
-        const uint32_t ch = (word >> (8 * b)) & 0xFFu;
-        const uint32_t up = ch & 0xDFu;
-        const bool base = (up == 'A' || up == 'C' || up == 'G' || up == 'T') && s + j < n && j < jend;
-        uint32_t c = (ch >> 1) & 3u;                           // A 0, C 1, T 2, G 3
-        c ^= c >> 1;                                           // A 0, C 1, G 2, T 3
-        fwd = ((fwd << 2) | c) & kmask;
-        rev = (rev >> 2) | ((uint64_t)(3u - c) << rshift);
-        run = base ? run + 1 : 0;
-        bases += (base && j < COUNT_RUN && s + j >= own_from) ? 1u : 0u;
-        if (run >= (uint32_t)k) {                              // (j < jend: the window starts at j - k + 1 < 32)
-          ++kmers;
-          sum += window((canonical && rev < fwd) ? rev : fwd);
-        }
-      }
-    }
-  }
-  return sum;
-}
 
 // One add per wave of the lanes' 64-bit sum (nothing when the sum is 0).
 __device__ inline void wave_add64(unsigned long long* cell, unsigned long long v) {
@@ -74,7 +30,7 @@ __global__ __launch_bounds__(256) void k_sketch_note(const uint8_t* text, uint64
   uint32_t bases = 0, kmers = 0, noted = 0;
   for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g * COUNT_RUN < n;
        g += (uint64_t)gridDim.x * blockDim.x)
-    noted += count_lane_walk(text, n, g * COUNT_RUN, own_from, k, canonical, bases, kmers, [=](uint64_t key) {
+    noted += count_lane(text, n, g * COUNT_RUN, own_from, k, canonical, bases, kmers, [=](uint64_t key) {
       if (key == EMPTY) return 0u;
       kmsketch::note(
           sketch, kmsketch::slot_of(key, shift), [](uint64_t* p) { return *p; },
@@ -95,7 +51,7 @@ __global__ __launch_bounds__(256) void k_count_solid(const uint8_t* text, uint64
   const uint64_t s = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * COUNT_RUN;
   uint32_t bases = 0, kmers = 0, tally = 0;              // tally: claimed | allt << 8 | admitted << 16 (each <= 32)
   if (s < n)
-    tally = count_lane_walk(text, n, s, own_from, k, canonical, bases, kmers, [=](uint64_t key) {
+    tally = count_lane(text, n, s, own_from, k, canonical, bases, kmers, [=](uint64_t key) {
       if (key == EMPTY) return 1u << 8;
       if (!kmsketch::admits(sketch, kmsketch::slot_of(key, shift))) return 0u;
       return (1u << 16) | count_add(tab, smask, key, 1u, meta);

@@ -16,6 +16,7 @@ import pytest
 
 from km_amd import lib as kmlib
 import test_count as tc
+from test_count_filter_cpu import canonical_key
 import test_count_quality as tq
 import test_scan as ts
 import test_scan_cpu as sc
@@ -221,6 +222,103 @@ def test_count_every_k(monkeypatch, k, canonical):
             assert stats["distinct"] == want[0].size, ctx
             if k == 32 and not canonical:                    # T^32, counted beside the table
                 assert n_all_t > 100 and int(got[0][-1]) == ALL_T and int(got[1][-1]) == n_all_t, ctx
+
+
+def corpus_stream(k, canonical):
+    """data, n_bases, n_all_t and the (text, cut) of the two add_text calls, as test_count_every_k feeds them."""
+    reads = corpus_case(k, canonical)["reads"]
+    data = b"\n".join(reads)
+    n_bases = len(data.translate(None, bytes(set(range(256)) - set(BASES))))
+    text = fasta_text(reads)
+    cut = text.index(reads[12][122:183]) + 30
+    assert len(reads[12]) == 2049 and text[cut - 30:cut + 30].count(b"\n") == 0
+    n_all_t = sum(r[i:i + 32].upper() == b"T" * 32 for r in reads for i in range(len(r) - 31))
+    return data, n_bases, text, cut, n_all_t
+
+
+@gpu
+@pytest.mark.parametrize("canonical", [True, False])
+@pytest.mark.parametrize("k", EVERY_K)
+def test_count_filtered_every_k(monkeypatch, k, canonical):
+    """k_count_filtered, both tiers: the filter is the table's keys and one key the corpus does not hold."""
+    case = corpus_case(k, canonical)
+    data, n_bases, _, _, n_all_t = corpus_stream(k, canonical)
+    model = dict(zip(*(a.tolist() for a in count_model(k, canonical))))
+    keys = sorted(case["table"])
+    assert all(canonical_key(key, k, canonical) == key for key in keys)
+    stranger = next((x for x in range(min(4 ** k, 1 << 20)) if canonical_key(x, k, canonical) == x and x not in model), None)
+    assert stranger is not None or k <= 5                    # (only a tiny key space is all in the corpus)
+    if stranger is not None:
+        keys.append(stranger)
+    want = {key: model.get(key, 0) for key in keys}
+    assert sum(want.values()) > 0 and (0 in want.values() or stranger is None) and set(want) != set(model)
+    order = np.array(sorted(want), np.uint64)
+    want_rec = (order, np.array([want[key] for key in order.tolist()], np.uint32))
+    slots = 64
+    while slots < 2 * len(want):
+        slots <<= 1
+    monkeypatch.setenv("KM_COUNT_FILTER_BLOCKS", "1")
+    # pieces that overlap by k - 1 bytes, then one block that makes several trips over one piece; either in both tiers
+    for stage, force_hbm in ((4096, False), (4096, True), (None, False), (None, True)):
+        if stage:
+            monkeypatch.setenv("KM_COUNT_STAGE_BYTES", str(stage))
+        else:
+            monkeypatch.setenv("KM_COUNT_STAGE_BYTES", str(1 << 17))
+            assert len(data) > 256 * 32                      # (a block of 256 lanes of 32 starts: two trips or three)
+        if force_hbm:
+            monkeypatch.setenv("KM_COUNT_FILTER_LDS", "0")
+        else:
+            monkeypatch.delenv("KM_COUNT_FILTER_LDS", raising=False)
+        c = kmlib.Counter(k=k, canonical=canonical)
+        try:
+            c.set_filter(np.array(keys, np.uint64))
+            c.add_bases(data)
+            stats, fs = c.stats(), c.filter_stats()
+            c.finish(0).close()
+            got = tc.sorted_records(c)
+        finally:
+            c.close()
+        ctx = (k, canonical, stage, force_hbm)
+        assert tc.same(got, want_rec), ctx
+        assert fs["tier"] == ("hbm" if force_hbm or slots > 2 * fs["lds_keys"] else "lds"), ctx
+        assert fs["kmers_hit"] == sum(want.values()) and fs["n_keys"] == len(want) == stats["distinct"], ctx
+        assert stats["bases"] == n_bases and stats["kmers"] == case["n_windows"], ctx
+        if k == 32 and not canonical:                        # T^32: in the filter, counted beside the table
+            assert n_all_t > 100 and want[ALL_T] == n_all_t and int(got[0][-1]) == ALL_T and int(got[1][-1]) == n_all_t, ctx
+
+
+@gpu
+@pytest.mark.parametrize("canonical", [True, False])
+@pytest.mark.parametrize("k", EVERY_K)
+def test_count_solid_every_k(monkeypatch, k, canonical):
+    """k_sketch_note through add_bases, k_count_solid through two add_text calls cut mid-line."""
+    case = corpus_case(k, canonical)
+    data, n_bases, text, cut, n_all_t = corpus_stream(k, canonical)
+    keys, counts = count_model(k, canonical)
+    want = (keys[counts >= 2], counts[counts >= 2])
+    assert 0 < want[0].size and (want[0].size < keys.size or k <= 5)
+    noted = case["n_windows"] - (n_all_t if k == 32 and not canonical else 0)
+    for stage in (None, 4096):                               # one piece; pieces that overlap by k - 1 bytes
+        if stage:
+            monkeypatch.setenv("KM_COUNT_STAGE_BYTES", str(stage))
+        c = kmlib.Counter(k=k, canonical=canonical)
+        try:
+            c.set_sketch(kmlib.sketch_words(int(keys.size)))
+            c.add_bases(data)
+            c.sketch_done()
+            used = c.add_text(text[:cut], final=False)
+            assert 0 < used <= cut
+            assert c.add_text(text[used:], final=True) == len(text) - used
+            stats, ss = c.stats(), c.sketch_stats()
+            c.finish(2).close()
+            got = tc.sorted_records(c)
+        finally:
+            c.close()
+        ctx = (k, canonical, stage)
+        assert tc.same(got, want), ctx
+        assert ss["kmers_noted"] == noted and stats["kmers"] == case["n_windows"] and stats["bases"] == n_bases, ctx
+        if k == 32 and not canonical:
+            assert n_all_t > 100 and int(got[0][-1]) == ALL_T and int(got[1][-1]) == n_all_t, ctx
 
 
 # ------------------------------------------------------------------ (b) the scan

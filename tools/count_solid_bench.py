@@ -16,8 +16,8 @@ of 16 MiB no table that has taken such a piece is smaller than 2^25 slots, whate
 pieces small enough for the keys to set the size.
 
 Fields: plain / solid: kernel_ms (best; solid: pass 1 + pass 2), kernel_ms_median, kernel_ms_all, wall_ms (best), slots,
-n_grow, distinct (keys in the table); solid also note_ms, count_ms (of the best pass), sketch_words, sketch_bits_1,
-sketch_bits_2; kmers_solid (records after the cut at 2: equal for both, asserted, as are the records themselves),
+n_grow, distinct (keys in the table); solid also note_ms, count_ms (of the best pass), note_ms_all, count_ms_all (of
+every pass), sketch_words, sketch_bits_1, sketch_bits_2; kmers_solid (records after the cut at 2: equal for both, asserted, as are the records themselves),
 kmers_singleton (distinct k-mers seen once), kmers_admitted (keys the solid counter's table held), false_positives
 (admitted - solid).
 
@@ -140,6 +140,7 @@ def main():
         if name == "solid":
             out[name].update({key: best[key] for key in ("note_ms", "count_ms", "sketch_words", "sketch_bits_1",
                                                          "sketch_bits_2")})
+            out[name].update(note_ms_all=[r["note_ms"] for r in rows], count_ms_all=[r["count_ms"] for r in rows])
     print(json.dumps(out))
 
 

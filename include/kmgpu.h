@@ -876,6 +876,49 @@ int km_select_pair_add_fastq(km_select_pair_t* s, const char* text1, uint64_t n1
 int km_select_pair_stats(km_select_pair_t* s, km_select_pair_stats_t* stats);
 int km_select_pair_destroy(km_select_pair_t* s);
 
+/* ---- select, labels: one output per label of a table, split on the device ------------------- */
+/* The rule (this project's own definition: the reference has no labelled selection to compare with):
+ *   A label table is an uploaded kmjf_t whose "count" of a k-mer is a 32-bit mask: bit l is set when the k-mer belongs to
+ *   label l, 0 <= l < n_labels <= 32.  Bits at or above n_labels are ignored.  A mask of 0xFFFF or more lives in the
+ *   table's overflow side table like any count of that size; kmjf_from_records sizes that table from the records, so any
+ *   number of such keys is fine.
+ *   The input, its validation, record r, the quality masking and the windows of a record are those of km_select above.
+ *   hits_l(r) is the number of windows of k bytes of record r's sequence line that are all ACGTacgt after the masking and
+ *   whose k-mer's mask has bit l.
+ *   keep_l(r) = hits_l(r) >= min_hits, with min_hits >= 1.  There is no invert.
+ *   Output l is the records with keep_l, byte for byte from the unmasked text, in input order.  A record kept by several
+ *   labels is in each of their outputs.
+ *   If the last record of a stream (final != 0) lacks its final newline, every output that ends with that record gets one
+ *   '\n' behind it: km_select's rule, applied per output.
+ *   The virtual stream of a piece is label 0's bytes of the piece, then label 1's, and so on; its length is the piece's
+ *   total.  The device gathers it into an output buffer of km_select's size, cap bytes (the buffer rounded down to 16) per
+ *   pass: pass p holds bytes [p * cap, min((p + 1) * cap, total)).  A piece takes max(1, ceil(total / cap)) passes;
+ *   gather_passes counts them over all pieces.
+ * Limits: n_labels * KM_COUNT_STAGE_BYTES < 2^32 (all offsets of a piece are 32-bit); device memory grows with n_labels:
+ *   one hit plane of stage / 4 and one length plane of about stage / 6 entries per label.
+ * Not covered: more than 32 labels (class ids instead of masks), pairs, invert, FASTA reads, more than one device. */
+typedef struct km_select_labels km_select_labels_t;
+/* records_any: records kept by at least one label, records_multi: by at least two */
+typedef struct { uint64_t records_in, records_any, records_multi, bytes_in, pieces, gather_passes; } km_select_labels_stats_t;
+/* As km_select_create, with out_fds[0 .. n_labels), label l's descriptor.  The checks come in km_select_create's order:
+ * KM_E_ARG for null pointers, min_hits == 0, min_qual_char outside 0..255, n_labels == 0 or > 32 and two equal
+ * descriptors; KM_E_STATE without an uploaded table; KM_E_IO for a descriptor that is not open; then KM_E_CAPACITY,
+ * naming both numbers, when n_labels * KM_COUNT_STAGE_BYTES >= 2^32. */
+int km_select_labels_create(kmjf_t* h, uint32_t n_labels, const int* out_fds, uint32_t min_hits, int min_qual_char,
+                            void* stream, km_select_labels_t** out);
+/* text, n, final, *consumed and every error as for km_select_add_fastq: a malformed record is KM_E_FORMAT with kind and
+ * byte offset, a record longer than a staging buffer KM_E_CAPACITY, a failed write KM_E_IO; what the pieces before the
+ * failing one kept is on the descriptors, and the selector is dead afterwards. */
+int km_select_labels_add_fastq(km_select_labels_t* s, const char* text, uint64_t n, int final, uint64_t* consumed);
+/* records_out[l], bytes_out[l] for l < n_labels; bytes_out counts a newline written behind a last record without one */
+int km_select_labels_stats(km_select_labels_t* s, km_select_labels_stats_t* stats, uint64_t* records_out, uint64_t* bytes_out);
+int km_select_labels_destroy(km_select_labels_t* s);
+/* hits[l * cap + r] = hits_l(r) for every record of text[0 .. n), as kmjf_fastq_hits gives hits(r); KM_E_ARG in addition
+ * for n_labels == 0 or > 32.  KM_SELECT_TIME=1 fills km_select_kernel_ms for both calls of this section, with the same
+ * four spans: [2] holds the sizes of all labels, the one scan and the offsets, [3] every gather pass. */
+int kmjf_fastq_label_hits(kmjf_t* h, uint32_t n_labels, const char* text, uint64_t n, int min_qual_char, uint32_t* hits,
+                          uint64_t cap, uint64_t* n_records, void* stream);
+
 /* ---- measurement helpers (bench.py at N = 1 holds no device buffers of its own) ------------- */
 int km_device_sync(int device);                                    /* hipDeviceSynchronize on `device`          */
 /* device-to-device copy of `bytes` bytes, `reps` times: read + write GB/s (the box's large-copy

@@ -502,10 +502,14 @@ def main_bait(args, err=None):
     Paired-end: `bait ... -1 R1.fq[.gz] [-1 ...] -2 R2.fq[.gz] [-2 ...] -o out_1.fq -O out_2.fq [--pair-rule any|both|sum]
     [--no-name-check]` keeps or drops the mates of a pair together (km_amd.count.select_pair_files), so the two outputs
     line up record for record; the figures are then #pairs_in, #pairs_out, #bytes_in_1/2, #bytes_out_1/2, #pieces and
-    #pair_rule."""
+    #pair_rule.
+
+    One file per label: `bait --split-dir DIR ...` is main_bait_split."""
     err = sys.stderr if err is None else err
     from . import count as kc
     from . import lib
+    if args.split_dir is not None:
+        return main_bait_split(args, err)
     db = None
     try:
         if args.db is not None:
@@ -539,6 +543,63 @@ def main_bait(args, err=None):
         return
     for key, name in (("records_in", "reads_in"), ("records_out", "reads_out"), ("bytes_in", "bytes_in"),
                       ("bytes_out", "bytes_out"), ("pieces", "pieces")):
+        err.write("#%s:%d\n" % (name, stats[key]))
+
+
+def split_labels(args):
+    """The labels of `bait --split-dir`, on the host and without a GPU -> (k, [dict as count.rows_labels gives them]).
+    With -t: one label per target file after directory expansion, named by the file's stem (find_mutation's Query),
+    its keys the canonical k-mers of the file's records; two files with one stem are a ValueError."""
+    import numpy as np
+    from . import count as kc
+    k = 31 if args.mer_len is None else args.mer_len
+    if args.rows is not None:
+        return k, kc.rows_labels(sys.stdin if args.rows == "-" else args.rows, k, with_ref=args.with_ref,
+                                 info="vs_ref" if args.info is None else args.info)
+    files = [f for t in args.targets for f in list_target_files([t])]
+    labels, seen = [], {}
+    for f in files:
+        stem = os.path.splitext(os.path.basename(f))[0]
+        if stem in seen:
+            raise ValueError("%s and %s have one stem, %s: every label needs a name of its own" % (seen[stem], f, stem))
+        seen[stem] = f
+        labels.append({"name": stem, "query": "", "type": "", "variant_name": "", "allele": "target",
+                       "keys": np.unique(kc.query_keys(k, True, seq_files=[f]))})
+    if len(labels) > kc.MAX_LABELS:
+        raise ValueError("%d target files give %d labels, more than the %d of one run: split the run" % (
+            len(files), len(labels), kc.MAX_LABELS))
+    return k, labels
+
+
+def main_bait_split(args, err):
+    """`bait --split-dir DIR (-t targets [-t ...] | --rows TSV [--with-ref] [-i INFO]) [-m K] [-n N] [-Q C] reads ...`:
+    one FASTQ per label in DIR, DIR/<label>.fq, from one pass over the reads (km_amd.count.select_label_files), and
+    DIR/labels.tsv with label, query, type, variant_name, allele, kmers, reads, bytes per label.  A read that carries
+    k-mers of several labels is in each of their files.  The figures go to standard error."""
+    from . import count as kc
+    from . import lib
+    db = None
+    try:
+        k, labels = split_labels(args)
+        if not labels:
+            raise ValueError("no labels: %s" % ("no row of the TSV was taken" if args.rows is not None else "no target files"))
+        db = kc.label_table([lab["keys"] for lab in labels], k, True, device=default_device())
+        n_kmers = int(db.info.n_records)
+        stats = kc.select_label_files(db, [lab["name"] for lab in labels], args.reads, args.split_dir,
+                                      min_hits=args.min_hits, min_qual_char=args.min_qual_char)
+        with open(os.path.join(args.split_dir, "labels.tsv"), "w") as fh:
+            fh.write("label\tquery\ttype\tvariant_name\tallele\tkmers\treads\tbytes\n")
+            for lab, reads, nbytes in zip(labels, stats["records_out"], stats["bytes_out"]):
+                fh.write("%s\t%s\t%s\t%s\t%s\t%d\t%d\t%d\n" % (lab["name"], lab["query"], lab["type"], lab["variant_name"],
+                                                             lab["allele"], lab["keys"].size, reads, nbytes))
+    except (lib.KmError, ValueError, OSError) as e:
+        sys.exit("ERROR: bait: %s" % e)
+    finally:
+        if db is not None:
+            db.close()
+    err.write("#labels:%d\n#bait_kmers:%d\n" % (len(labels), n_kmers))
+    for key, name in (("records_in", "reads_in"), ("records_any", "reads_any"), ("records_multi", "reads_multi"),
+                      ("bytes_in", "bytes_in"), ("pieces", "pieces"), ("gather_passes", "gather_passes")):
         err.write("#%s:%d\n" % (name, stats[key]))
 
 
@@ -690,6 +751,17 @@ def build_parser():
                     help="with -1/-2: N k-mers in either mate (any, the default), in each mate (both) or in the two together (sum)")
     bt.add_argument("--no-name-check", action="store_true",
                     help="with -1/-2: do not compare the mates' names (a /1 or /2 at the end is ignored by the check)")
+    bt.add_argument("--split-dir", default=None, metavar="DIR",
+                    help="one FASTQ per label in DIR, split on the GPU in one pass over the reads: with -t one label per "
+                         "target file, with --rows one per variant row; DIR/labels.tsv lists them")
+    bt.add_argument("--rows", default=None, metavar="TSV",
+                    help="with --split-dir: the labels are the variant rows of this find_mutation TSV (- is stdin), the "
+                         "k-mers of a row's Sequence that its Reference_sequence lacks; the TSV does not record its k: "
+                         "give the k of the run that wrote it with -m (default: -m 31)")
+    bt.add_argument("--with-ref", action="store_true",
+                    help="with --rows: also a .ref label per row, the reference k-mers that the variant lacks")
+    bt.add_argument("-i", "--info", default=None, metavar="INFO",
+                    help="with --rows: take the rows whose Info column matches INFO (default: vs_ref)")
     bt.add_argument("reads", nargs="*", help="4-line FASTQ files, plain or gzip; - is stdin")
     return parser
 
@@ -710,7 +782,8 @@ def _looks_like_target(path):
 def parse_args(argv=None, parser=None):
     """build_parser().parse_args plus what argparse cannot say on its own, refused the same way (exit status 2):
     `dump -t` without `-c`, `query` with neither -s nor a MER, `count` with --solid beside --if, `merge` with more than one of --max / --min /
-    --subtract, `bait` without exactly one of -t / -d or with -m beside -d, without reads, with unequal numbers of -1 and
+    --subtract, `bait --split-dir` beside any of -v, -o, -O, -d, -1, -2 or without exactly one of -t / --rows, --rows
+    without --split-dir, --with-ref or -i without --rows, `bait` without exactly one of -t / -d or with -m beside -d, without reads, with unequal numbers of -1 and
     -2, with plain reads beside them, with -1/-2 but not both of -o and -O or with one path for both, and with -O,
     --pair-rule or --no-name-check but no -1/-2."""
     parser = build_parser() if parser is None else parser
@@ -724,7 +797,19 @@ def parse_args(argv=None, parser=None):
     if args._cmd == "query" and not args.sequence and not args.mers:
         parser.error("query: nothing to query: give -s FILE or MER arguments")
     if args._cmd == "bait":
-        if bool(args.targets) == (args.db is not None):
+        if args.split_dir is not None:
+            if args.invert or args.output is not None or args.output2 is not None or args.db is not None \
+                    or args.mate1 or args.mate2:
+                parser.error("bait: --split-dir goes with none of -v, -o, -O, -d, -1 and -2")
+            if bool(args.targets) == (args.rows is not None):
+                parser.error("bait: --split-dir takes its labels from exactly one of -t targets.fa and --rows TSV")
+            if args.rows == "-" and "-" in args.reads:
+                parser.error("bait: --rows - reads the TSV from standard input, so the reads cannot be - as well")
+        elif args.rows is not None:
+            parser.error("bait: --rows goes with --split-dir only")
+        if args.rows is None and (args.with_ref or args.info is not None):
+            parser.error("bait: --with-ref and -i go with --rows only")
+        if args.rows is None and bool(args.targets) == (args.db is not None):
             parser.error("bait: give exactly one of -t targets.fa and -d db.jf")
         if args.db is not None and args.mer_len is not None:
             parser.error("bait: -m goes with -t only: a -d file has its own k")

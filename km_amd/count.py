@@ -322,6 +322,124 @@ def select_files(db, paths, out=None, min_hits=1, invert=False, min_qual_char=No
             return sel.stats()
 
 
+MAX_LABELS = 32                           # km_select_labels_*: one bit of a 32-bit mask per label
+
+
+def label_table(label_keys, k, canonical, device=0):
+    """The label table of lib.LabelSelector, uploaded: `label_keys` is a list of uint64 key arrays, one per label (at
+    most 32; a label may have none); the table holds the union of the keys, and a key's "count" is the mask of the
+    labels that have it (bit l = label l) -> Database.  The union and the masks are made on the host with numpy."""
+    label_keys = [np.ascontiguousarray(keys, np.uint64).reshape(-1) for keys in label_keys]
+    if not 1 <= len(label_keys) <= MAX_LABELS:
+        raise ValueError("%d labels: a label table holds 1 to %d" % (len(label_keys), MAX_LABELS))
+    every = np.concatenate(label_keys)
+    bits = np.concatenate([np.full(keys.size, 1 << l, np.uint32) for l, keys in enumerate(label_keys)])
+    keys, inverse = np.unique(every, return_inverse=True)
+    masks = np.zeros(keys.size, np.uint32)
+    np.bitwise_or.at(masks, inverse.reshape(-1), bits)
+    db = _lib.Database.from_records(keys, masks, k, canonical)
+    try:
+        db.upload(device)
+    except BaseException:
+        db.close()
+        raise
+    return db
+
+
+_TSV_COLUMNS = ("Query", "Type", "Variant_name", "Sequence", "Reference_sequence", "Info")
+
+
+def _label_kmers(seq, without, k):
+    """The canonical k-mers of `seq` upper-cased that are no k-mers of `without`, distinct and ascending."""
+    from . import kmer as km
+    sets = []
+    for text in (seq, without):
+        keys = _windows(np.frombuffer(text.upper().encode("latin-1"), np.uint8), k)
+        sets.append(np.unique(np.minimum(keys, km.revcomp(keys, k))) if keys.size else keys)
+    return np.ascontiguousarray(np.setdiff1d(sets[0], sets[1]), np.uint64)
+
+
+def rows_labels(tsv, k, with_ref=False, info="vs_ref"):
+    """The labels of the variant rows of a `find_mutation` TSV (a path or a file object of text lines): '#' lines and
+    the header line are skipped, and a row is taken when its Info column matches `info` (re.search, as `find_report -i`
+    reads it), its Type is not Reference and its Sequence is not empty.  Taken row i (from 1) gives the label
+    "%02d_<Query>_<Type>.alt" (characters outside [A-Za-z0-9._-] become '_') whose keys are the canonical k-mers of
+    Sequence, upper-cased, that Reference_sequence does not have; with_ref adds "....ref" with the two sequences
+    exchanged.  A label may have no keys (the .ref label of an ITD: every reference k-mer lies on its path too).
+    -> a list of dicts with name, query, type, variant_name, allele ("alt" / "ref") and keys, in label order.
+    More than 32 labels raise ValueError; nothing here touches the GPU.  The TSV does not record its k: `k` must be
+    the k of the run that wrote it."""
+    import re
+    if isinstance(tsv, (str, bytes, os.PathLike)):
+        with open(tsv, "r") as fh:
+            lines = fh.read().splitlines()
+    else:
+        lines = [ln.decode("latin-1") if isinstance(ln, bytes) else ln for ln in tsv.read().splitlines()]
+    want = re.compile(info)
+    col, rows = None, []
+    for line in lines:
+        if not line.strip() or line.startswith("#"):
+            continue
+        cells = line.split("\t")
+        if cells[:2] == ["Database", "Query"]:
+            col = {name: cells.index(name) for name in _TSV_COLUMNS}
+            continue
+        if col is None:
+            raise ValueError("a row comes before the header line (Database, Query, ...)")
+        if len(cells) <= max(col.values()):
+            raise ValueError("a row has %d columns, fewer than the header names" % len(cells))
+        row = {name: cells[at] for name, at in col.items()}
+        if want.search(row["Info"]) and row["Type"] != "Reference" and row["Sequence"]:
+            rows.append(row)
+    per = 2 if with_ref else 1
+    if len(rows) * per > MAX_LABELS:
+        raise ValueError("%d variant rows give %d labels, more than the %d of one run: split the run (fewer rows per "
+                         "TSV, a narrower -i, or without --with-ref)" % (len(rows), len(rows) * per, MAX_LABELS))
+    labels = []
+    for i, row in enumerate(rows, 1):
+        stem = re.sub(r"[^A-Za-z0-9._-]", "_", "%02d_%s_%s" % (i, row["Query"], row["Type"]))
+        for allele, seq, other in (("alt", row["Sequence"], row["Reference_sequence"]),
+                                   ("ref", row["Reference_sequence"], row["Sequence"]))[:per]:
+            labels.append({"name": "%s.%s" % (stem, allele), "query": row["Query"], "type": row["Type"],
+                           "variant_name": row["Variant_name"], "allele": allele, "keys": _label_kmers(seq, other, k)})
+    return labels
+
+
+def select_label_files(db, names, paths, out_dir, min_hits=1, min_qual_char=None, block=BLOCK):
+    """select_files with one output per label: `db` is a label table (label_table) of len(names) labels, and the reads
+    of the 4-line FASTQ files `paths` whose windows of k bases with label l's bit number at least min_hits go to
+    out_dir/<names[l]>.fq, byte for byte and in input order, file after file (lib.LabelSelector: one pass over the
+    reads, split on the GPU) -> the dict of km_select_labels_stats_t with records_out and bytes_out as lists and
+    `files`, the paths written.  The pre-flight checks of select_files run before anything is created; out_dir is
+    created if absent; a label file this call created is removed again when the call fails."""
+    if isinstance(paths, (str, bytes)):
+        paths = [paths]
+    paths, names = list(paths), list(names)
+    if not 1 <= len(names) <= MAX_LABELS:
+        raise ValueError("%d labels: one run takes 1 to %d" % (len(names), MAX_LABELS))
+    if len(set(names)) != len(names):
+        raise ValueError("two labels have one name: every label needs a file of its own")
+    _preflight(paths)
+    os.makedirs(out_dir, exist_ok=True)
+    files = [os.path.join(out_dir, name + ".fq") for name in names]
+    with contextlib.ExitStack() as stack:
+        fds = [stack.enter_context(_text_out(path)) for path in files]
+        with _lib.LabelSelector(db, fds, min_hits=min_hits, min_qual_char=min_qual_char) as sel:
+            for path in paths:
+                blocks = _Blocks(path, block)
+                try:
+                    for buf in blocks:
+                        blocks.used(sel.add_fastq(buf, final=False))
+                    sel.add_fastq(blocks.tail, final=True)   # (always: an empty one still ends the file's stream)
+                except _lib.KmError as e:
+                    raise _lib.KmError(e.code, "%s: %s" % (path, e.detail)) from e
+                finally:
+                    blocks.close()
+            stats = sel.stats()
+    stats["files"] = files
+    return stats
+
+
 def merge_files(paths, mode="sum", lower_count=1, device=0, expected_distinct=0, keep_counter=False,
                 upper_count=0xFFFFFFFF):
     """Merge `binary/sorted` files of one k and one canonical setting into one table on the GPU.  Per key the counts

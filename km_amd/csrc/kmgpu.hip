@@ -28,6 +28,9 @@
 //                  (count_host.h's front half of a FASTQ piece, a Staging in, the kept bytes out through TextDrain)
 //   select_pair_host.h  km_select_pair_*: the same for the two mate streams of a paired-end run, kept or dropped as
 //                  pairs (select_host.h's SelDev per mate, a Staging in and a TextDrain out per mate)
+//   select_label_host.h  km_select_labels_*, kmjf_fastq_label_hits: the FASTQ records sorted into one output per label
+//                  of a table whose counts are label masks (the same front half, a Staging in, one Staging out whose
+//                  bytes LabelDrain cuts at the label boundaries; included last)
 //   filter_host.h  km_counter_set_filter, km_counter_filter_stats: a counter that counts only a given set of k-mers
 //                  (the seed of its table, the tier and the cap of its bounded grid)
 //   sketch_host.h  km_sketch_words, km_sketch_slot, km_counter_set_sketch, km_counter_sketch_done,
@@ -84,7 +87,9 @@
 #include "select_pair_kernel.h"
 #include "select_pair_rule.h"
 #include "filter_kernel.h"      // (behind those above: every kernel before it keeps its place in the code object)
-#include "sketch_kernel.h"      // (last, for the same reason)
+#include "sketch_kernel.h"      // (behind filter_kernel.h, for the same reason)
+#include "select_label_kernel.h"   // (last, for the same reason)
+#include "select_label_rule.h"
 
 using namespace kmd;
 
@@ -105,3 +110,4 @@ using namespace kmd;
 #include "select_pair_host.h"
 #include "filter_host.h"
 #include "sketch_host.h"        // (behind filter_host.h: it uses its grid cap)
+#include "select_label_host.h"  // (behind select_host.h: its SelCore and span cells; last: its kernels are the last)

@@ -117,9 +117,14 @@ KM_SCAN_HD inline U128 source_bytes(Load& load, uint32_t sp, uint32_t c) {
 // `total` are zero.  rec_off[0 .. n_rec]: the exclusive scan of the record lengths, rec_off[n_rec] = total.  The record
 // of the word's first byte comes from one binary search (the last r with rec_off[r] <= 16 w: dropped records have
 // length 0 and are passed over), the records behind it by stepping, with another search where the step meets a dropped one.
-template <typename Load>
-KM_SCAN_HD inline U128 gather_word(Load& load, const uint32_t* line_start, const uint32_t* rec_off, uint32_t n_rec,
-                                   uint32_t total, uint32_t w) {
+// gather_word_of is the same over entries that are not the records themselves: entry e of rec_off holds the bytes of
+// record rec_of(e), which is asked only for entries of a length > 0 (select_label_rule.h: the labels' planes end to end).
+struct SameRecord {
+  KM_SCAN_HD uint32_t operator()(uint32_t e) const { return e; }
+};
+template <typename Load, typename RecOf>
+KM_SCAN_HD inline U128 gather_word_of(Load& load, const uint32_t* line_start, const uint32_t* rec_off, uint32_t n_rec,
+                                      uint32_t total, uint32_t w, const RecOf& rec_of) {
   uint32_t o = w * WORD;
   const uint32_t end = total - o < WORD ? total : o + WORD;
   uint32_t r = (uint32_t)kmscan::seq_of(rec_off, 0, (uint64_t)n_rec - 1, o);
@@ -128,7 +133,7 @@ KM_SCAN_HD inline U128 gather_word(Load& load, const uint32_t* line_start, const
   uint32_t filled = 0;
   for (;;) {
     const uint32_t c = (r_end < end ? r_end : end) - o;
-    const uint32_t sp = record_begin(line_start, r) + (o - r_begin);
+    const uint32_t sp = record_begin(line_start, rec_of(r)) + (o - r_begin);
     out = bytes_or(out, bytes_up(bytes_first(source_bytes(load, sp, c), c), filled));
     filled += c;
     o += c;
@@ -143,6 +148,11 @@ KM_SCAN_HD inline U128 gather_word(Load& load, const uint32_t* line_start, const
     }
   }
   return out;
+}
+template <typename Load>
+KM_SCAN_HD inline U128 gather_word(Load& load, const uint32_t* line_start, const uint32_t* rec_off, uint32_t n_rec,
+                                   uint32_t total, uint32_t w) {
+  return gather_word_of(load, line_start, rec_off, n_rec, total, w, SameRecord{});
 }
 
 }  // namespace kmsel

@@ -53,6 +53,8 @@ SYMBOLS = [
     "km_select_create", "km_select_add_fastq", "km_select_stats", "km_select_destroy", "kmjf_fastq_hits",
     "km_select_kernel_ms",
     "km_select_pair_create", "km_select_pair_add_fastq", "km_select_pair_stats", "km_select_pair_destroy",
+    "km_select_labels_create", "km_select_labels_add_fastq", "km_select_labels_stats", "km_select_labels_destroy",
+    "kmjf_fastq_label_hits",
     "km_device_count", "km_stream_create", "km_stream_destroy", "km_version",
 ]
 
@@ -112,6 +114,12 @@ class SelectPairStats(C.Structure):
     _fields_ = [("pairs_in", C.c_uint64), ("pairs_out", C.c_uint64), ("bytes_in", C.c_uint64 * 2),
                 ("bytes_out", C.c_uint64 * 2), ("pieces", C.c_uint64), ("resent_bytes", C.c_uint64 * 2),
                 ("reserved", C.c_uint64 * 3)]
+
+
+class SelectLabelsStats(C.Structure):
+    """km_select_labels_stats_t (include/kmgpu.h)."""
+    _fields_ = [("records_in", C.c_uint64), ("records_any", C.c_uint64), ("records_multi", C.c_uint64),
+                ("bytes_in", C.c_uint64), ("pieces", C.c_uint64), ("gather_passes", C.c_uint64)]
 
 
 class TextState(C.Structure):
@@ -354,6 +362,11 @@ def load():
         "km_select_pair_add_fastq": [vp, vp, u64, vp, u64, i32, C.POINTER(u64), C.POINTER(u64)],
         "km_select_pair_stats": [vp, C.POINTER(SelectPairStats)],
         "km_select_pair_destroy": [vp],
+        "km_select_labels_create": [vp, u32, C.POINTER(i32), u32, i32, vp, C.POINTER(vp)],
+        "km_select_labels_add_fastq": [vp, vp, u64, i32, C.POINTER(u64)],
+        "km_select_labels_stats": [vp, C.POINTER(SelectLabelsStats), C.POINTER(u64), C.POINTER(u64)],
+        "km_select_labels_destroy": [vp],
+        "kmjf_fastq_label_hits": [vp, u32, vp, u64, i32, vp, u64, C.POINTER(u64), vp],
         "km_device_count": [C.POINTER(i32)],
         "km_device_sync": [i32],
         "km_device_copy_GBs": [i32, u64, i32, C.POINTER(dbl)],
@@ -593,6 +606,19 @@ class Database(_Handle):
                                         _qual_byte(min_qual_char or 0), ptr(hits), hits.size, C.byref(n),
                                         C.c_void_p(stream or 0)))
         return hits[:n.value].copy()
+
+    def fastq_label_hits(self, n_labels, text, min_qual_char=None, stream=None):
+        """kmjf_fastq_label_hits: this table's counts read as label masks (bit l = label l, l < n_labels <= 32); per
+        label and record of the 4-line FASTQ text the number of windows of k bases whose k-mer's mask has the label's
+        bit -> np.uint32[n_labels, n_records].  Otherwise as fastq_hits."""
+        buf = _byte_view(text)
+        cap = buf.size // 6 + 1
+        hits = np.zeros((max(int(n_labels), 1), cap), np.uint32)
+        n = C.c_uint64()
+        check(self._lib.kmjf_fastq_label_hits(self._h, int(n_labels), ptr(buf) if buf.size else None, buf.size,
+                                              _qual_byte(min_qual_char or 0), ptr(hits), cap, C.byref(n),
+                                              C.c_void_p(stream or 0)))
+        return hits[:, :n.value].copy()
 
 
 def _byte_view(data):
@@ -994,6 +1020,45 @@ def select_kernel_ms():
     ms = (C.c_float * 4)()
     check(load().km_select_kernel_ms(ms))
     return {"front": float(ms[0]), "hits": float(ms[1]), "sizes": float(ms[2]), "gather": float(ms[3])}
+
+
+class LabelSelector(_Handle):
+    """The FASTQ reads sorted into one output per label on the GPU (km_select_labels_*, include/kmgpu.h): the counts of
+    `db` are label masks (count.label_table), read r goes to outs[l] iff its windows of k bases whose k-mer's mask has
+    bit l number at least min_hits, byte for byte and in input order; a read kept by several labels is in each of their
+    outputs.  `outs`: one descriptor, or file object with fileno(), per label, at most 32.  `db` must stay open for as
+    long as the selector lives.  A context manager; close() releases the device side."""
+    _slot, _destroy, _live = "_s", "km_select_labels_destroy", _LIVE_COUNTERS
+
+    def __init__(self, db, outs, min_hits=1, min_qual_char=None, stream=None):
+        self._lib = load()
+        self._s = C.c_void_p()
+        self._db = db
+        fds = [out_descriptor(o) for o in outs]
+        self.n_labels = len(fds)
+        arr = (C.c_int32 * max(len(fds), 1))(*fds)
+        check(self._lib.km_select_labels_create(db._h, len(fds), arr, int(min_hits), _qual_byte(min_qual_char or 0),
+                                                C.c_void_p(stream or 0), C.byref(self._s)))
+        self._opened()
+
+    def add_fastq(self, data, final=False):
+        """As Selector.add_fastq: returns how many bytes were taken (whole records); what the call kept is on the
+        descriptors when it returns."""
+        buf = _byte_view(data)
+        consumed = C.c_uint64()
+        check(self._lib.km_select_labels_add_fastq(self._s, ptr(buf) if buf.size else None, buf.size, int(bool(final)),
+                                                   C.byref(consumed)))
+        return int(consumed.value)
+
+    def stats(self):
+        """km_select_labels_stats_t as a dict, with records_out and bytes_out as lists, one entry per label."""
+        st = SelectLabelsStats()
+        rec, byt = (C.c_uint64 * self.n_labels)(), (C.c_uint64 * self.n_labels)()
+        check(self._lib.km_select_labels_stats(self._s, C.byref(st), rec, byt))
+        out = {name: int(getattr(st, name)) for name, _ in SelectLabelsStats._fields_}
+        out["records_out"] = [int(v) for v in rec]
+        out["bytes_out"] = [int(v) for v in byt]
+        return out
 
 
 PAIR_RULES = {"any": 0, "both": 1, "sum": 2}     # KM_PAIR_ANY, KM_PAIR_BOTH, KM_PAIR_SUM

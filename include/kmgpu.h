@@ -570,6 +570,50 @@ int km_counter_set_jf(km_counter_t* c, const char* path, int op, uint64_t* n_rec
  * (km_counter_records, km_counter_write_jf, km_counter_histo, km_counter_dump) works on what was kept. */
 int km_counter_finish_range(km_counter_t* c, uint32_t lower_count, uint32_t upper_count, kmjf_t** out);
 
+/* ---- comparing tables that already exist -----------------------------------------------------------
+ * How several tables relate to each other ("Compare"): every call below that feeds records is ONE input,
+ * however many staging pieces it spans; inputs are numbered 0 .. n - 1 in the order of the calls, an input without
+ * records is an input too, and a counter takes at most 32.  All inputs are of the counter's k and canonical setting.
+ *   Set of an input.  Input i is the set S_i of the keys of its records with lower <= count <= upper.  A record with
+ *     count 0 is absent whatever lower is.  The cut is applied per record: a key that appears in several records of one
+ *     input is in S_i if ANY of them passes the cut, and feeding a record twice changes nothing (membership is
+ *     idempotent).  upper < lower is an empty set and no error.
+ *   Result.  shared[i][j] = |S_i & S_j|, symmetric, shared[i][i] = |S_i|.  union = |S_0 | .. | S_n-1|.
+ *     in_exactly[m], 1 <= m <= n, = the keys held by exactly m inputs; in_exactly[n] is the core.  private[i] = the keys
+ *     held by input i alone.  All values are 64-bit integers and exact.
+ * The result depends neither on the order of the records nor on the piece size.  On the device a key's count cell holds
+ * the 32-bit mask of the inputs that have it, so every input crosses to the device once, whatever the number of pairs,
+ * and any input may grow the table (the mask moves with the key).  These are THIS PROJECT'S OWN definitions.
+ * State (each refusal before any device work, the counter left as it was and still usable; KM_E_STATE unless said
+ * otherwise, km_last_error names which): a counter that has taken text, FASTQ, sum / max or set records refuses the mark
+ * calls, and a counter that has taken a mark call refuses all of those; a 33rd mark call is KM_E_CAPACITY; a counter
+ * with a filter or a sketch takes no records.  km_counter_finish / _finish_range, _records, _write_jf, _histo and _dump
+ * of such a counter are refused: its count cells are not counts.  km_counter_stats' distinct counts the union so far;
+ * km_counter_merge_stats tallies the records that passed the cut and, with KM_COUNT_TIME_MERGE=1, the marking kernels. */
+typedef struct {
+  uint32_t n_inputs;              /* mark calls so far                                                          */
+  float kernel_ms;                /* with KM_COUNT_TIME_MERGE=1 when the counter was made: the time of every pass
+                                     of km_counter_cooccurrence over the table so far, by HIP events; 0 otherwise */
+  uint64_t n_union;               /* union                                                                      */
+  uint64_t shared[32 * 32];       /* shared[i * 32 + j], the full symmetric matrix; 0 at i or j >= n_inputs     */
+  uint64_t in_exactly[33];        /* [m], 1 <= m <= n_inputs; [0] is 0                                          */
+  uint64_t private_to[32];        /* private[i]                                                                 */
+} km_cooc_t;
+/* n (key, count) pairs as the next input, packed and enqueued as km_counter_add_records does; n == 0 is an empty input. */
+int km_counter_mark_records(km_counter_t* c, const uint64_t* keys, const uint32_t* counts, uint64_t n, uint32_t lower,
+                            uint32_t upper);
+/* The record area of a file as the next input, read as km_counter_add_jf reads it, with its checks of the header and of
+ * k / canonical and their messages (a refused file is no input); *n_records (may be NULL): the records in the file.
+ * A call that fails AFTER those checks (KM_E_IO because the file ends before its records do, KM_E_NOMEM / KM_E_CAPACITY
+ * because the table cannot grow; the same holds for km_counter_mark_records) has taken its ordinal: it is an input, one
+ * of the 32, whose set is the records of the pieces enqueued before the failure.  The counter stays usable, but its
+ * result then speaks of that partial input: start over with a new counter for the numbers of the whole files. */
+int km_counter_mark_jf(km_counter_t* c, const char* path, uint32_t lower, uint32_t upper, uint64_t* n_records);
+/* The result over the inputs so far, in one streaming pass over the table, which is left as it was: it may be called
+ * between inputs and more than once (waits for everything enqueued).  T^32 of a non-canonical k = 32 table, which has
+ * no slot, is folded into every number on the host.  Without any input every number is 0. */
+int km_counter_cooccurrence(km_counter_t* c, km_cooc_t* out);
+
 /* ---- counting only a given set of k-mers -----------------------------------------------------------
  * What `jellyfish count --if FILE` is for ("Filtered counting"): a counter may be given a FILTER once,
  * before it has been fed anything.  The filter is a set of k-mers in the counter's key encoding; for a canonical

@@ -1,4 +1,4 @@
-"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, ``count``, ``merge``, ``histo``,
+"""``km find_mutation`` / ``km min_cov`` / ``km linear_kmin`` drop-in command line, ``count``, ``merge``, ``compare``, ``histo``,
 ``stats``, ``dump``, ``query``, ``cov`` and ``bait``.
 
 Same flags, same ``#key:value`` echo, same TSV and ``#Elapsed time`` trailer as
@@ -436,6 +436,32 @@ def main_merge(args, err=None):
         kc.dump_file(args.output, out=args.dump, fmt="column", device=default_device())
 
 
+def main_compare(args, out=None, err=None):
+    """How up to 32 .jf files of one k relate, counted on the GPU (km_amd.count.compare_files): file i is the set of its
+    k-mers with -L <= count <= -U, and every file crosses to the device once, whatever the number of pairs.  By default
+    a header and one row per pair i < j: a, b, distinct_a, distinct_b, shared, jaccard, contain_a, contain_b; --matrix
+    prints the square matrix of shared counts or of Jaccard indices instead.  --summary FILE gets one row per input
+    (input, records, distinct, private), --spectrum FILE "m<TAB>kmers" for the k-mers held by exactly m inputs.  One input
+    is legal and gives no pair rows.  This project's own semantics."""
+    err = sys.stderr if err is None else err
+    from . import count as kc
+    from .lib import KmError
+    try:
+        result, stats = kc.compare_files(args.inputs, lower_count=args.lower_count, upper_count=args.upper_count,
+                                         device=default_device())
+    except (ValueError, KmError) as e:
+        sys.exit("ERROR: compare: %s" % e)
+    n = result["n_inputs"]
+    for key, value in (("inputs", n), ("records_in", stats["records_in"]), ("union", result["union"]),
+                       ("core", int(result["in_exactly"][n])), ("slots", stats["slots"]), ("n_grow", stats["n_grow"])):
+        err.write("#%s:%d\n" % (key, value))
+    _write_text(kc.format_compare(args.inputs, result, args.matrix or "pairs"), args.output, out)
+    if args.summary:
+        _write_text(kc.format_compare(args.inputs, result, "summary"), args.summary)
+    if args.spectrum:
+        _write_text(kc.format_compare(args.inputs, result, "spectrum"), args.spectrum)
+
+
 def _write_text(text, path, out=None):
     if path:
         with open(path, "w") as fh:
@@ -695,6 +721,16 @@ def build_parser():
     mg.add_argument("--dump", metavar="FILE", default=None,
                     help="also write the records written (after -L) as text: byte for byte what `dump -c OUT` prints")
     mg.add_argument("inputs", nargs="+", metavar="db.jf", help="binary/sorted files of one k and one canonical setting")
+    cp = sub.add_parser("compare", help="the k-mers that up to 32 .jf files of one k share, pair by pair, counted on the GPU")
+    cp.add_argument("-L", "--lower-count", type=_count32, default=1, help="a file holds a k-mer only with count >= lower-count")
+    cp.add_argument("-U", "--upper-count", type=_count32, default=0xFFFFFFFF, help="a file holds a k-mer only with count <= upper-count")
+    cp.add_argument("--matrix", choices=("shared", "jaccard"), default=None,
+                    help="print the square matrix of shared k-mers or of Jaccard indices instead of the rows per pair")
+    cp.add_argument("--summary", metavar="FILE", default=None, help="also write one row per input: input, records, distinct, private")
+    cp.add_argument("--spectrum", metavar="FILE", default=None,
+                    help="also write m<TAB>kmers for m = 1 .. n: the k-mers that exactly m inputs hold")
+    cp.add_argument("-o", "--output", default=None, help="output file (default: standard output)")
+    cp.add_argument("inputs", nargs="+", metavar="db.jf", help="binary/sorted files of one k and one canonical setting, at most 32")
     hs = sub.add_parser("histo", add_help=False,
                         help="histogram of the counts of a .jf file, on the GPU (-h is --high as in Jellyfish: help is "
                              "--help only)")
@@ -860,6 +896,8 @@ def main(argv=None):
         main_count(args)
     elif cmd == "merge":
         main_merge(args)
+    elif cmd == "compare":
+        main_compare(args)
     elif cmd == "histo":
         main_histo(args)
     elif cmd == "stats":

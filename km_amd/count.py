@@ -491,6 +491,99 @@ def merge_files(paths, mode="sum", lower_count=1, device=0, expected_distinct=0,
     return db, stats
 
 
+MAX_COMPARE_INPUTS = 32
+COMPARE_FORMS = ("pairs", "shared", "jaccard", "summary", "spectrum")
+
+
+def compare_files(paths, lower_count=1, upper_count=0xFFFFFFFF, device=0):
+    """How up to 32 `binary/sorted` files of one k and one canonical setting relate, counted on the GPU in one table
+    whose count cells are membership masks (Counter.mark_jf, Counter.cooccurrence): file i is the set of the keys of its
+    records with lower_count <= count <= upper_count, and the result holds, for every pair, how many keys both sets
+    have -> (result, stats).  result is Counter.cooccurrence()'s dict (n_inputs, union, shared[n, n], in_exactly[n + 1],
+    private[n]) plus records = the record count of every file; stats: k, canonical, records_in (records that passed the
+    cut), distinct, slots, n_grow, mark_ms and cooc_ms (the two kernels' times, 0 without KM_COUNT_TIME_MERGE=1).
+
+    Every header is read first (lib.jf_file_info, no GPU): no file, more than 32, a file that cannot be read, or one
+    whose k or canonical differs from the first file's raises ValueError, naming the number of inputs, before a counter
+    exists.  Every file crosses to the device once, whatever the number of pairs.  This project's own definitions
+    (include/kmgpu.h)."""
+    if isinstance(paths, (str, bytes)):
+        paths = [paths]
+    paths = list(paths)
+    if not paths:
+        raise ValueError("0 inputs: nothing to compare")
+    if len(paths) > MAX_COMPARE_INPUTS:
+        raise ValueError("%d inputs: one run compares at most %d" % (len(paths), MAX_COMPARE_INPUTS))
+    infos = []
+    for p in paths:
+        try:
+            infos.append(_lib.jf_file_info(p))
+        except _lib.KmError as e:
+            raise ValueError("input %d of %d: %s" % (len(infos) + 1, len(paths), e)) from None
+    first = infos[0]
+    for p, info in zip(paths, infos):
+        if (info["k"], info["canonical"]) != (first["k"], first["canonical"]):
+            raise ValueError("%s holds k=%d canonical=%s, but %s (the first of %d inputs) holds k=%d canonical=%s" % (
+                p, info["k"], info["canonical"], paths[0], len(paths), first["k"], first["canonical"]))
+    size = max(info["n_records"] for info in infos)
+    counter = _lib.Counter(k=first["k"], canonical=first["canonical"], device=device, expected_distinct=size)
+    try:
+        for p in paths:
+            counter.mark_jf(p, lower_count, upper_count)
+        result = counter.cooccurrence()
+        merged = counter.merge_stats()
+        stats = counter.stats()
+    finally:
+        counter.close()
+    result["records"] = [int(info["n_records"]) for info in infos]
+    return result, {"k": first["k"], "canonical": first["canonical"], "records_in": merged["records_in"],
+                    "distinct": stats["distinct"], "slots": stats["slots"], "n_grow": stats["n_grow"],
+                    "mark_ms": merged["kernel_ms"], "cooc_ms": result.pop("kernel_ms")}
+
+
+def _ratio(num, den):
+    return "%.6f" % (num / den) if den else "NA"
+
+
+def format_compare(names, result, what="pairs"):
+    """The text of `compare` from a result of compare_files (n^2 numbers: built on the host), tab-separated:
+      "pairs"     a header, then one row per pair i < j in the order (0,1), (0,2), .., (1,2), ..: a, b, distinct_a,
+                  distinct_b, shared, jaccard = shared / (distinct_a + distinct_b - shared), contain_x = shared / distinct_x;
+      "shared" / "jaccard"   the square matrix, the names as header row (behind an empty cell) and first column;
+      "summary"   a header, then one row per input: input, records, distinct, private;
+      "spectrum"  one row "m<TAB>kmers" for m = 1 .. n, without a header.
+    Ratios are printed %.6f, or NA where the denominator is 0."""
+    if what not in COMPARE_FORMS:
+        raise ValueError("what %r is none of %s" % (what, ", ".join(repr(w) for w in COMPARE_FORMS)))
+    names = [os.fsdecode(x) for x in names]
+    n = int(result["n_inputs"])
+    if len(names) != n:
+        raise ValueError("%d names for %d inputs" % (len(names), n))
+    shared = [[int(v) for v in row] for row in result["shared"]]
+    jaccard = lambda i, j: _ratio(shared[i][j], shared[i][i] + shared[j][j] - shared[i][j])
+    lines = []
+    if what == "pairs":
+        lines.append("a\tb\tdistinct_a\tdistinct_b\tshared\tjaccard\tcontain_a\tcontain_b")
+        for i in range(n):
+            for j in range(i + 1, n):
+                s, da, db = shared[i][j], shared[i][i], shared[j][j]
+                lines.append("%s\t%s\t%d\t%d\t%d\t%s\t%s\t%s" % (names[i], names[j], da, db, s, jaccard(i, j), _ratio(s, da),
+                                                                 _ratio(s, db)))
+    elif what in ("shared", "jaccard"):
+        lines.append("\t".join([""] + names))
+        for i in range(n):
+            cells = [str(shared[i][j]) if what == "shared" else jaccard(i, j) for j in range(n)]
+            lines.append("\t".join([names[i]] + cells))
+    elif what == "summary":
+        lines.append("input\trecords\tdistinct\tprivate")
+        for i in range(n):
+            lines.append("%s\t%d\t%d\t%d" % (names[i], int(result["records"][i]), shared[i][i], int(result["private"][i])))
+    else:
+        for m in range(1, n + 1):
+            lines.append("%d\t%d" % (m, int(result["in_exactly"][m])))
+    return "".join(line + "\n" for line in lines)
+
+
 def histo_file(path, low=1, high=10000, increment=1, lower_count=1, upper_count=0xFFFFFFFF, device=0):
     """The histogram of the counts of a `binary/sorted` file and its four statistics, what `jellyfish histo -l low
     -h high -i increment` and `jellyfish stats` print -> (base, bins ndarray uint64, stats dict), as Counter.histo.

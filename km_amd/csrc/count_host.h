@@ -34,8 +34,9 @@ const char* fastq_error_text(unsigned kind) {
 }
 }  // namespace
 
-// What a counter has been fed: text, FASTQ and sum / max records (plain), or the inputs of one set operation.
-enum { FEED_NONE = 0, FEED_PLAIN = 1, FEED_SET = 2 };
+// What a counter has been fed: text, FASTQ and sum / max records (plain), the inputs of one set operation, or the
+// inputs of a comparison (mark_host.h), whose count cells are membership masks.
+enum { FEED_NONE = 0, FEED_PLAIN = 1, FEED_SET = 2, FEED_MARK = 3 };
 
 // What a counter does with the windows of its text, i.e. which kernel launch_insert launches: every key inserted; only
 // the keys of a filter counted, probed in LDS or in HBM (filter_host.h); or, with a sketch (sketch_host.h), every key
@@ -65,6 +66,9 @@ struct km_counter {
   int feed = FEED_NONE;                   // what the counter has taken: the two kinds do not mix (setops_host.h)
   int set_op = 0;                         // FEED_SET: KM_SET_INTERSECT / KM_SET_SUBTRACT
   uint32_t set_inputs = 0;                // FEED_SET: inputs so far, the empty ones too
+  uint32_t mark_inputs = 0;               // FEED_MARK: inputs so far, the empty ones too (mark_host.h)
+  KernelSpans cooc_spans;                 // KM_COUNT_TIME_MERGE: around every pass of k_cooc_table (mark_host.h)
+  DevBuf<unsigned long long> cooc_cells;  // FEED_MARK: what k_cooc_table adds to, allocated by the first call
   CountMode mode = COUNT_PLAIN;           // set by km_counter_set_filter, km_counter_set_sketch, km_counter_sketch_done
   uint32_t grid_cap = 0;                  // the most blocks of a launch with a bounded grid (filtered, noting)
   KernelSpans insert_spans;               // KM_COUNT_TIME_FILTER: around every insert launch, filtered or not
@@ -99,6 +103,17 @@ static int counter_takes_plain(const km_counter* c) {
   if (c->feed == FEED_SET)
     return fail(KM_E_STATE, "counter holds the inputs of a set operation (%s): it takes no text, FASTQ or sum / max records",
                 c->set_op == KM_SET_INTERSECT ? "intersect" : "subtract");
+  if (c->feed == FEED_MARK)
+    return fail(KM_E_STATE, "counter holds the inputs of a comparison (mark): it takes no text, FASTQ or sum / max records");
+  return KM_OK;
+}
+
+// ... and every call that reads count cells as counts (finish, records, write_jf, histo, dump): those of a counter
+// that holds the inputs of a comparison are membership masks (mark_host.h)
+static int counter_holds_counts(const km_counter* c, const char* what) {
+  if (c->feed == FEED_MARK)
+    return fail(KM_E_STATE, "counter holds the inputs of a comparison (mark): its count cells are membership masks, and %s "
+                "has nothing to read; km_counter_cooccurrence is its result", what);
   return KM_OK;
 }
 
@@ -265,7 +280,7 @@ extern "C" int km_counter_create(int device, int k, int canonical, uint64_t expe
   c->device = device;
   c->k = k;
   c->canonical = canonical ? 1 : 0;
-  if (const char* e = getenv("KM_COUNT_TIME_MERGE")) c->merge_spans.timed = atoi(e) != 0;
+  if (const char* e = getenv("KM_COUNT_TIME_MERGE")) c->merge_spans.timed = c->cooc_spans.timed = atoi(e) != 0;
   if (const char* e = getenv("KM_COUNT_TIME_FILTER")) c->insert_spans.timed = atoi(e) != 0;
   c->slots = COUNT_DEFAULT_SLOTS;
   if (expected_distinct) {
@@ -469,9 +484,11 @@ extern "C" int km_counter_stats(km_counter_t* c, km_counter_stats_t* s) {
 // km_counter_finish / km_counter_finish_range: the slots that survived (every slot unless the counter holds a set
 // operation) with lower <= count <= upper into the record arrays, then the lookup table from those.  `ranged` = the
 // compaction of setops_kernel.h; without it, the one of count_kernel.h that km_counter_finish has always used.
-static int counter_finish_cut(km_counter* c, uint32_t lower_count, uint32_t upper_count, bool ranged, kmjf_t** out) {
+static int counter_finish_cut(km_counter* c, uint32_t lower_count, uint32_t upper_count, bool ranged, kmjf_t** out,
+                              const char* caller = "km_counter_finish") {
   KMCHK(counter_usable(c));
   KMCHK(counter_sketch_settled(c));
+  KMCHK(counter_holds_counts(c, caller));
   HIPCHK(hipSetDevice(c->device));
   int rc = counter_flush(c);
   unsigned long long m[CM_WORDS];
@@ -527,6 +544,7 @@ extern "C" int km_counter_finish(km_counter_t* c, uint32_t lower_count, kmjf_t**
 extern "C" int km_counter_records(km_counter_t* c, uint64_t* keys, uint32_t* counts, uint64_t cap, uint64_t* n) {
   if (!c || !n) return fail(KM_E_ARG, "null argument");
   KMCHK(counter_sketch_settled(c));
+  KMCHK(counter_holds_counts(c, "km_counter_records"));
   if (!c->finished) return fail(KM_E_STATE, "km_counter_finish comes first");
   *n = c->n_out;
   if (!keys && !counts) return KM_OK;

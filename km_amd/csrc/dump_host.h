@@ -289,6 +289,7 @@ extern "C" int km_counter_dump(km_counter_t* c, int out_fd, int format, uint32_t
   if (!c) return fail(KM_E_ARG, "null argument");
   KMCHK(dump_check_format(format));
   KMCHK(dump_check_fd(out_fd));
+  KMCHK(counter_holds_counts(c, "km_counter_dump"));
   if (!c->finished) return fail(KM_E_STATE, "km_counter_finish comes first");
   g_dump_kernel_ms = 0.f;
   if (stats) memset(stats, 0, sizeof *stats);

@@ -154,6 +154,7 @@ extern "C" int km_counter_histo(km_counter_t* c, uint64_t low, uint64_t high, ui
   KMCHK(histo_capacity(lay, bins, cap));
   if (c->fq_error != FQ_NO_ERROR) return counter_format_failed(c);
   KMCHK(counter_sketch_settled(c));
+  KMCHK(counter_holds_counts(c, "km_counter_histo"));
   if (!c->finished && c->feed == FEED_SET)              // (setops_host.h) the live table holds keys that do not survive
     return fail(KM_E_STATE, "the counter holds the inputs of a set operation: km_counter_finish comes before its histogram");
   r.rounds = histo_rounds();

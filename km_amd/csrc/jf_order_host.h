@@ -201,6 +201,7 @@ extern "C" int km_jf_sort_records(int device, const uint64_t* columns, int k, in
 // once the counter has finished: the copy of one piece runs while the piece before it is written to the file.
 extern "C" int km_counter_write_jf(km_counter_t* c, const char* path, const char* cmdline_json, uint64_t seed) {
   if (!c || !path) return fail(KM_E_ARG, "null argument");
+  KMCHK(counter_holds_counts(c, "km_counter_write_jf"));
   if (!c->finished) return fail(KM_E_STATE, "km_counter_finish comes first");
   const uint64_t n = c->n_out;
   if (n >> 32) return fail(KM_E_ARG, "%llu records: the bucket directory is 32-bit", (unsigned long long)n);

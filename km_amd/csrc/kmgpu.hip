@@ -30,12 +30,16 @@
 //                  pairs (select_host.h's SelDev per mate, a Staging in and a TextDrain out per mate)
 //   select_label_host.h  km_select_labels_*, kmjf_fastq_label_hits: the FASTQ records sorted into one output per label
 //                  of a table whose counts are label masks (the same front half, a Staging in, one Staging out whose
-//                  bytes LabelDrain cuts at the label boundaries; included last)
+//                  bytes LabelDrain cuts at the label boundaries; the last with templated kernels of its own)
 //   filter_host.h  km_counter_set_filter, km_counter_filter_stats: a counter that counts only a given set of k-mers
 //                  (the seed of its table, the tier and the cap of its bounded grid)
 //   sketch_host.h  km_sketch_words, km_sketch_slot, km_counter_set_sketch, km_counter_sketch_done,
 //                  km_counter_sketch_stats: a counter fed twice, whose table takes only the k-mers a first pass saw
 //                  again (the sketch, the end of its first pass, its statistics)
+//   mark_host.h    km_counter_mark_records, km_counter_mark_jf, km_counter_cooccurrence: the inputs of a comparison as
+//                  membership masks in the count cells, pieces on the counter's staging, and the one pass over the table
+//                  that counts what every pair of inputs shares (included last; its two kernels are not templates, and the
+//                  compiler emits those ahead of the template instances: every existing kernel keeps its instructions)
 // Their order is load-bearing: the templated kernels enter the code object in the order in which the host code
 // first instantiates them, and the code object is compared byte for byte across host-only changes.  The two instances
 // of k_count_filtered are instantiated by count_host.h's launch_insert since all counting kernels are launched from
@@ -88,8 +92,11 @@
 #include "select_pair_rule.h"
 #include "filter_kernel.h"      // (behind those above: every kernel before it keeps its place in the code object)
 #include "sketch_kernel.h"      // (behind filter_kernel.h, for the same reason)
-#include "select_label_kernel.h"   // (last, for the same reason)
+#include "select_label_kernel.h"   // (behind sketch_kernel.h, for the same reason)
 #include "select_label_rule.h"
+#include "mark_kernel.h"        // (behind all others, with cooc_kernel.h: no existing kernel changes its instructions)
+#include "cooc_kernel.h"
+#include "cooc_rule.h"
 
 using namespace kmd;
 
@@ -110,4 +117,5 @@ using namespace kmd;
 #include "select_pair_host.h"
 #include "filter_host.h"
 #include "sketch_host.h"        // (behind filter_host.h: it uses its grid cap)
-#include "select_label_host.h"  // (behind select_host.h: its SelCore and span cells; last: its kernels are the last)
+#include "select_label_host.h"  // (behind select_host.h: its SelCore and span cells)
+#include "mark_host.h"          // (behind all others: it instantiates no templated kernel)

@@ -16,6 +16,9 @@ int set_check(const km_counter* c, int op) {
   if (c->feed == FEED_PLAIN)
     return fail(KM_E_STATE, "counter has taken text, FASTQ or sum / max records: a set operation (%s) needs a counter of its own",
                 set_name(op));
+  if (c->feed == FEED_MARK)
+    return fail(KM_E_STATE, "counter holds the inputs of a comparison (mark): a set operation (%s) needs a counter of its own",
+                set_name(op));
   if (c->feed == FEED_SET && c->set_op != op)
     return fail(KM_E_STATE, "counter holds the inputs of %s: it cannot take one of %s", set_name(c->set_op), set_name(op));
   return KM_OK;
@@ -80,5 +83,5 @@ extern "C" int km_counter_set_jf(km_counter_t* c, const char* path, int op, uint
 
 extern "C" int km_counter_finish_range(km_counter_t* c, uint32_t lower_count, uint32_t upper_count, kmjf_t** out) {
   if (!c || !out) return fail(KM_E_ARG, "null argument");
-  return counter_finish_cut(c, lower_count, upper_count, true, out);
+  return counter_finish_cut(c, lower_count, upper_count, true, out, "km_counter_finish_range");
 }

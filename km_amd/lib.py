@@ -45,6 +45,7 @@ SYMBOLS = [
     "km_counter_write_jf",
     "km_jf_file_info", "km_counter_add_records", "km_counter_add_jf", "km_counter_merge_stats",
     "km_counter_set_records", "km_counter_set_jf", "km_counter_finish_range",
+    "km_counter_mark_records", "km_counter_mark_jf", "km_counter_cooccurrence",
     "km_counter_set_filter", "km_counter_filter_stats",
     "km_sketch_words", "km_sketch_slot", "km_counter_set_sketch", "km_counter_sketch_done", "km_counter_sketch_stats",
     "km_histo_layout", "km_counter_histo", "km_jf_histo", "km_histo_kernel_ms", "km_histo_text", "km_histo_stats_text",
@@ -89,6 +90,12 @@ class CounterStats(C.Structure):
     """km_counter_stats_t (include/kmgpu.h)."""
     _fields_ = [("bases", C.c_uint64), ("kmers", C.c_uint64), ("distinct", C.c_uint64), ("slots", C.c_uint64),
                 ("n_grow", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Cooc(C.Structure):
+    """km_cooc_t"""
+    _fields_ = [("n_inputs", C.c_uint32), ("kernel_ms", C.c_float), ("n_union", C.c_uint64),
+                ("shared", C.c_uint64 * (32 * 32)), ("in_exactly", C.c_uint64 * 33), ("private_to", C.c_uint64 * 32)]
 
 
 class HistoStats(C.Structure):
@@ -328,6 +335,9 @@ def load():
         "km_counter_set_records": [vp, vp, vp, u64, i32],
         "km_counter_set_jf": [vp, cp, i32, C.POINTER(u64)],
         "km_counter_finish_range": [vp, u32, u32, C.POINTER(vp)],
+        "km_counter_mark_records": [vp, vp, vp, u64, u32, u32],
+        "km_counter_mark_jf": [vp, cp, u32, u32, C.POINTER(u64)],
+        "km_counter_cooccurrence": [vp, C.POINTER(Cooc)],
         "km_counter_set_filter": [vp, vp, u64],
         "km_counter_filter_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32), C.POINTER(u64),
                                     C.POINTER(C.c_float)],
@@ -750,6 +760,36 @@ class Counter(_Handle):
         n = C.c_uint64()
         check(self._lib.km_counter_set_jf(self._c, os.fsencode(path), _set_op(op), C.byref(n)))
         return int(n.value)
+
+    def mark_records(self, keys, counts, lower_count=1, upper_count=0xFFFFFFFF):
+        """km_counter_mark_records: (key, count) pairs as the NEXT input of a comparison (at most 32).  The input is the
+        set of the keys of its pairs with lower_count <= count <= upper_count; pairs with count 0 are absent, keys may
+        repeat (a key is in the set if any of its pairs passes the cut), an empty call is an empty input.  This
+        project's own definitions (include/kmgpu.h)."""
+        keys, counts = _records(keys, counts)
+        check(self._lib.km_counter_mark_records(self._c, ptr(keys) if keys.size else None,
+                                                ptr(counts) if counts.size else None, keys.size, int(lower_count),
+                                                int(upper_count)))
+
+    def mark_jf(self, path, lower_count=1, upper_count=0xFFFFFFFF):
+        """km_counter_mark_jf: the records of a `binary/sorted` file of the counter's k and canonical as the next
+        input of the comparison, as by mark_records; returns the number of records in the file."""
+        n = C.c_uint64()
+        check(self._lib.km_counter_mark_jf(self._c, os.fsencode(path), int(lower_count), int(upper_count), C.byref(n)))
+        return int(n.value)
+
+    def cooccurrence(self):
+        """km_counter_cooccurrence (waits for everything marked so far; the counter is left as it was): dict(n_inputs,
+        union, shared = uint64[n, n] with |S_i & S_j|, in_exactly = uint64[n + 1] indexed by m (entry 0 is 0), private =
+        uint64[n], kernel_ms = the time of the passes over the table so far, needs KM_COUNT_TIME_MERGE=1 when the
+        counter is made)."""
+        r = Cooc()
+        check(self._lib.km_counter_cooccurrence(self._c, C.byref(r)))
+        n = int(r.n_inputs)
+        shared = np.ctypeslib.as_array(r.shared).reshape(32, 32)[:n, :n].copy()
+        return {"n_inputs": n, "union": int(r.n_union), "shared": shared,
+                "in_exactly": np.ctypeslib.as_array(r.in_exactly)[:n + 1].copy(),
+                "private": np.ctypeslib.as_array(r.private_to)[:n].copy(), "kernel_ms": float(r.kernel_ms)}
 
     def set_filter(self, keys):
         """km_counter_set_filter: from now on only the k-mers of `keys` (uint64, the counter's key encoding; a
